@@ -26,8 +26,14 @@ call and the k8s action / gating path runs for every request), with EOS ignored 
 every request generates exactly ``--max-new-tokens`` tokens (the reference's tool call
 is ~20-60 tokens; default 48).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node 8 bench.py --gpus 8 ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (``ms_per_step`` =
+timed wall time / K).  Requests come from one seeded stream, so the same arguments give the same
+inputs in every run; ``--dump-outputs DIR`` writes the results of the last timed step's requests
+as ``DIR/<name>.npy``.  Measurements beyond the headline figure go behind ``--full``.  Llama-3-8B on
+one GPU runs its decode GEMMs by the static routing rule (``config.decode_routing``; see main()).
 
 ``--gpus N`` decides the world: under torchrun it must equal ``WORLD_SIZE`` (a mismatch is
 refused); without a launcher (no ``WORLD_SIZE`` in the environment) and N > 1 this process
@@ -104,9 +110,13 @@ def parse():
     ap.add_argument("--token-align-wave", type=int, default=0,
                     help="steps longer than this many rows are trimmed to a multiple of it (4096: whole "
                          "waves of 256x256 tiles on the N=4096 projections); 0: off")
-    ap.add_argument("--admission", choices=["deferred", "inline", "threaded"], default="deferred",
+    ap.add_argument("--admission", choices=["stepped", "deferred", "inline", "threaded"], default="stepped",
                     help="continuous mode, how retrieval for newly freed slots runs on the engine thread: "
-                         "deferred (default) launches query encoder + kNN on a side stream and admits the "
+                         "stepped (default) launches query encoder + kNN on a side stream and admits the "
+                         "requests one loop iteration later, waiting for the top-k if it has not landed, so "
+                         "the admitting engine step does not depend on host timing and runs repeat (measured on "
+                         "MI355X, interleaved: stepped 110.7 / 110.4 / 110.0 q/s, p50 1154-1159 ms, deferred "
+                         "109.2 q/s, p50 1167 ms, host kNN wait 0.1 ms either way); deferred launches the same and admits the "
                          "requests at the first loop iteration after their top-k landed -- the host never "
                          "blocks on the device; inline waits for the top-k before the next step "
                          "(measured on MI355X, 2 runs each: 98.7/98.8 q/s either way, deferred p50 +3 ms, "
@@ -140,6 +150,16 @@ def parse():
                     help="with --tp-sim: JSON of the measured per-call TP tail collective floor "
                          "(benchmarks/xgmi_floor.py --world 2; default profiles/r4_tp_collectives/floor_tp2_h<H>.json)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the results of the last timed step's --batch requests, in "
+                         "the order of the seeded request stream, as DIR/<name>.npy (float32 / float64): "
+                         "request_index, query_crc32, output_ids, evidence_scores, output_tokens, prompt_tokens, "
+                         "status.  Not with --via-http")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement or check beyond the headline figure (baselines, other "
+                         "configurations, comparisons with a reference).  A plain run sets up, warms up, times "
+                         "--steps steps and prints the result line; anything more belongs behind this option "
+                         "(at present there is nothing more, so it changes nothing)")
     return ap.parse_args()
 
 
@@ -154,6 +174,10 @@ def main():
         args.admit_chunk = max(1, args.batch // 8)
     if args.via_http:  # before any GPU use: the servers are child processes
         import subprocess
+
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the in-process timed path's results; "
+                             "--via-http runs the servers as child processes and has none to write")
 
         cmd = [sys.executable, os.path.join(ROOT, "benchmarks", "http_bench.py"), "--docs", str(args.docs),
                "--max-new-tokens", str(args.max_new_tokens), "--model", args.model, "--embedder", args.embedder,
@@ -214,6 +238,18 @@ def main():
     from llm_kubernetes_minikube_sharp4dev_amd.rag.synthetic import make_queries
 
     on_gpu = args.device == "cuda"
+    # Llama-3-8B on one GPU (the headline configuration, no TP) runs its decode GEMMs by the static
+    # routing rule: the start-up tuner (LK_DECODE_TUNE=1, the package default) times the
+    # weight-streaming kernel against the prefill GEMM per shape, near-equal arms fall either way
+    # from run to run, and two runs over the same requests then compute them with different
+    # kernels (other rounding, other greedy picks at near-ties).  Measured on one MI355X,
+    # interleaved, --steps 8 --warmup 2: static 110.3 / 110.1 / 110.1 q/s, tuned 111.6 / 110.6.
+    # Every other configuration keeps the tuner (the static rule was off by up to 2.9x on the
+    # 70B TP=8 shard shapes); an exported LK_DECODE_TUNE wins.  The result line records which ran.
+    if (on_gpu and args.model == "llama-3-8b" and world == 1 and args.tp == 1 and args.tp_sim == 1):
+        os.environ.setdefault("LK_DECODE_TUNE", "0")
+    decode_routing = ("start-up tuner" if os.environ.get("LK_DECODE_TUNE", "1") == "1"
+                      else "static rule (LK_DECODE_TUNE=0)") if on_gpu else None
     if on_gpu and args.one_device:
         # several processes' hardware queues share the device: at 4 per process the scheduler
         # time-slices 8 ranks and every all-reduce waits for its peers' turn (0.08 vs 2.46 q/s at
@@ -404,11 +440,38 @@ def main():
         agent = AgentPipeline(engine, tok, k8s, cfg)
         pipe = {"rag": rag, "agent": agent, "mixed": MixedPipeline(rag, agent)}[args.workload]
         replica = rank // args.tp
-        qcount = [0]
+        # one seeded request stream per replica, generated in blocks of --batch queries and handed
+        # out in order: request i is the same query in every run with the same arguments, however
+        # many the closed loop asks for at a time (that depends on timing)
+        qcount, qbuf, issued = [0], collections.deque(), {}
 
         def next_queries(k):
-            qcount[0] += 1
-            return make_queries(k, seed=args.seed * 100003 + replica * 7919 + qcount[0])
+            while len(qbuf) < k:
+                qcount[0] += 1
+                qbuf.extend(make_queries(max(args.batch, 1), seed=args.seed * 100003 + replica * 7919 + qcount[0]))
+            qs = [qbuf.popleft() for _ in range(k)]
+            for q in qs:
+                assert q not in issued, f"query issued twice: {q!r}"  # (its ticket makes each unique)
+                issued[q] = len(issued)  # position in the stream
+            return qs
+
+        if args.dump_outputs:
+            # keep each request's generated token ids and the kNN scores of its evidence on its
+            # result (the pipelines return the decoded text, the citation ids and the tool call).
+            # The wrappers sit on the pipeline instances: ContinuousLoad, batch_step and
+            # MixedPipeline all call `<pipeline>.finish_request(...)`, which finds them first
+            def _note(obj, note):
+                fn = obj.finish_request
+
+                def finish_request(p, out_ids, ctx):
+                    r = fn(p, out_ids, ctx)
+                    note(r, out_ids, ctx)
+                    return r
+
+                obj.finish_request = finish_request
+
+            _note(rag, lambda r, ids, ctx: setattr(r, "evidence_scores", [h.score for h in ctx[1]] if ctx else []))
+            _note(pipe, lambda r, ids, ctx: setattr(r, "output_ids", list(ids)))
 
         def batch_step():
             reqs, tim = pipe.plan_requests(next_queries(args.batch))
@@ -444,17 +507,18 @@ def main():
                               f"{engine.launches}, timed completions {len(results)}")
 
             threading.Thread(target=_beat, name="bench-heartbeat", daemon=True).start()
-        load = None
+        load, warm = None, []
         if args.mode == "continuous":
             # warm-up fills the pipeline and reaches the steady prefill/decode mix; the timed
             # window continues the same stream (in-flight requests carry over)
             load = ContinuousLoad(pipe, next_queries, params, args.batch, admit_chunk=args.admit_chunk,
                                   threaded=args.admission == "threaded",
-                                  deferred=args.admission == "deferred")
-            load.run(max(args.warmup, 1) * args.batch)
+                                  deferred=args.admission in ("deferred", "stepped"),
+                                  stepped=args.admission == "stepped")
+            warm = load.run(max(args.warmup, 1) * args.batch)
         else:
             for _ in range(args.warmup):
-                batch_step()
+                warm = batch_step()
         tim_setup = time.perf_counter() - t_setup
         log(rank, f"setup {tim_setup:.1f}s; timing {args.steps} steps x {args.batch} req/replica")
 
@@ -513,6 +577,25 @@ def main():
                           "chars_per_token": round(dc / dt, 3), "evidence_chunks": round(de / dn, 2)}
         if load is not None:
             load_host = {k: v - load_host0[k] for k, v in load.host_s.items()}
+        if args.dump_outputs:
+            # the last timed step's requests: the --batch consecutive requests of the stream whose
+            # turn it was.  The closed loop completes requests a little out of order, so a few of
+            # them finish just before or just after that step: those still in flight are run to
+            # completion here, outside the timed window, by the same loop
+            first = ((max(args.warmup, 1) if load is not None else args.warmup) + args.steps - 1) * args.batch
+            by_index = {issued[r.prompt]: r for r in warm + results}
+            # (one more untimed step of --batch completions at a time: the loop stays in its steady,
+            # pipelined state, as in the window.  They are among the --batch requests in flight,
+            # so one step is enough and two bound it)
+            for _ in range(2):
+                if load is None or all(i in by_index for i in range(first, first + args.batch)):
+                    break
+                by_index.update((issued[r.prompt], r) for r in load.run(args.batch))
+            if any(i not in by_index for i in range(first, first + args.batch)):
+                raise SystemExit("bench.py: --dump-outputs: the last timed step's requests did not complete")
+            _dump_outputs(args.dump_outputs, [by_index[i] for i in range(first, first + args.batch)], first,
+                          args.max_new_tokens, cfg.rag.agent_topk, "" if rank == 0 else f".replica{replica}")
+        if load is not None:
             load.drain()
         if args.tp > 1:
             shutdown_tp(engine)
@@ -705,6 +788,7 @@ def main():
                              "greedy, ignore_eos" + (", tool-call grammar" if args.constrained else "")),
                 "prefix_caching": not args.no_prefix_cache,
                 "hip_graphs": not args.no_graphs,
+                "decode_routing": decode_routing,
                 # grammar-forced tokens appended by the host and run as extend chunks (every
                 # token still gets its forward pass; LK_JUMP_FORWARD=0 steps them one by one)
                 "jump_forward": bool(args.constrained and args.sampling == "greedy" and _jump_forward_on()),
@@ -785,6 +869,37 @@ def _launch_ranks(n: int) -> int:
     if rc == 0:
         rc = next((p.returncode for p in procs if p.returncode), 0)
     return rc if rc >= 0 else 128 - rc
+
+
+def _dump_outputs(path: str, last: list, first: int, max_new_tokens: int, topk: int, suffix: str = "") -> None:
+    """``--dump-outputs``: the results of the last timed step's requests as ``<name><suffix>.npy``,
+    row i = request ``first + i`` of the seeded stream (``request_index``), so two runs with the
+    same arguments hold the same requests row for row.  ``output_ids``: the generated token ids,
+    padded with -1 (all -1: answered without the LLM); ``evidence_scores``: the kNN cosine scores
+    of the evidence chunks that passed the citation gate, padded with 0 (agent requests: none);
+    ``status``: the HTTP status of the executed tool call; ``query_crc32``: CRC-32 of the query the
+    row's result carries (``result.prompt``), so a reader can check which request a row answers.
+    A few tens of kB in all."""
+    import zlib
+
+    import numpy as np
+
+    ids = np.full((len(last), max_new_tokens), -1.0, dtype=np.float32)
+    scores = np.zeros((len(last), topk), dtype=np.float32)
+    for i, r in enumerate(last):
+        t = getattr(r, "output_ids", [])[:max_new_tokens]
+        ids[i, :len(t)] = t
+        s = getattr(r, "evidence_scores", [])[:topk]
+        scores[i, :len(s)] = s
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("request_index", np.arange(first, first + len(last), dtype=np.float64)),
+                      ("query_crc32", np.array([zlib.crc32(r.prompt.encode()) for r in last], dtype=np.float64)),
+                      ("output_ids", ids),
+                      ("evidence_scores", scores),
+                      ("output_tokens", np.array([r.output_tokens for r in last], dtype=np.float32)),
+                      ("prompt_tokens", np.array([r.prompt_tokens for r in last], dtype=np.float32)),
+                      ("status", np.array([int(r.status) for r in last], dtype=np.float32))):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
 
 
 def _idle_summary(trace) -> dict:

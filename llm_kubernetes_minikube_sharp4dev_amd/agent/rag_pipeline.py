@@ -195,7 +195,7 @@ class ContinuousLoad:
     hand-offs cost the engine thread more than the overlap gains."""
 
     def __init__(self, pipe: RagAgentPipeline, next_queries, params, concurrency: int, admit_chunk: int = 16,
-                 threaded: bool = False, deferred: Optional[bool] = None):
+                 threaded: bool = False, deferred: Optional[bool] = None, stepped: bool = False):
         self.pipe, self.next_queries, self.params = pipe, next_queries, params
         self.concurrency, self.admit_chunk = concurrency, admit_chunk
         self.inflight: dict = {}
@@ -206,7 +206,13 @@ class ContinuousLoad:
         # engine step later than a blocking plan).  LK_ADMIT_DEFERRED=1 selects it.
         self.deferred = (os.environ.get("LK_ADMIT_DEFERRED", "0") == "1") if deferred is None else deferred
         self.deferred = self.deferred and hasattr(pipe, "plan_launch")  # pipelines without retrieval: inline
-        self._launched: list = []  # (t_adm, plan handle) in launch order
+        # stepped=True (with deferred): a launched retrieval is admitted exactly one loop iteration
+        # after its launch, waiting for its top-k if it has not landed, instead of at whichever
+        # iteration a poll first finds it landed -- the engine step that admits a request then
+        # does not depend on host timing, and two runs over the same requests batch them alike
+        self.stepped = stepped
+        self._iter = 0  # loop iterations of run() so far
+        self._launched: list = []  # (t_adm, plan handle, loop iteration of the launch) in launch order
         self._todo: "queue.Queue" = queue.Queue()
         self._ready: "queue.Queue" = queue.Queue()
         self._planning = 0  # queries submitted to the planner and not yet admitted
@@ -244,12 +250,16 @@ class ContinuousLoad:
         else:
             h = self.pipe.plan_launch(qs)
         self.host_s["plan"] += time.perf_counter() - t_adm
-        self._launched.append((t_adm, h))
+        self._launched.append((t_adm, h, self._iter))
 
     def _finish_launched(self, block: bool):
-        """Plans whose top-k landed (all of them when ``block``), in launch order."""
-        while self._launched and (block or self.pipe.plan_ready(self._launched[0][1])):
-            t_adm, h = self._launched.pop(0)
+        """Plans whose top-k landed -- ``stepped``: plans launched in an earlier loop iteration,
+        landed or not -- (all of them when ``block``), in launch order."""
+        def due(entry):
+            return entry[2] < self._iter if self.stepped else self.pipe.plan_ready(entry[1])
+
+        while self._launched and (block or due(self._launched[0])):
+            t_adm, h, _ = self._launched.pop(0)
             t0 = time.perf_counter()
             reqs, tim = self.pipe.requests_of(*self.pipe.plan_finish(h))
             self._ready.put((t_adm, time.perf_counter() - t0, reqs, tim))
@@ -323,6 +333,7 @@ class ContinuousLoad:
 
         try:
             while len(done) < n_complete:
+                self._iter += 1
                 free = self.concurrency - len(self.inflight) - self._planning
                 note = ""
                 if free >= min(self.admit_chunk, self.concurrency) or (not self.inflight and not self._planning):

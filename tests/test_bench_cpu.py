@@ -50,6 +50,62 @@ def test_bench_single_rank_json(workload):
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["parallelism"] == "dp1"
 
 
+def _stream_crcs(block, batch=2, seed=0):
+    """CRC-32 of the queries of one --batch block of bench.py's request stream (replica 0),
+    regenerated from the seed: block k holds requests (k - 1) * batch .. k * batch - 1."""
+    import zlib
+
+    from llm_kubernetes_minikube_sharp4dev_amd.rag.synthetic import make_queries
+
+    return [float(zlib.crc32(q.encode())) for q in make_queries(batch, seed=seed * 100003 + block)]
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the results of the last timed step's requests (one row per request,
+    float arrays, in the order of the seeded stream); --steps sets the timed steps; --full is
+    accepted; the same arguments give the same inputs and outputs in a second run."""
+    import numpy as np
+
+    names = {"request_index", "query_crc32", "output_ids", "evidence_scores", "output_tokens", "prompt_tokens",
+             "status"}
+    runs = []
+    for tag, extra in (("a", ["--full"]), ("b", [])):
+        d = _run(["--mode", "batch", "--steps", "2", "--dump-outputs", str(tmp_path / tag), *extra])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert {p.name for p in (tmp_path / tag).iterdir()} == {n + ".npy" for n in names}
+        runs.append({n: np.load(tmp_path / tag / f"{n}.npy") for n in names})
+    a, b = runs
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["output_ids"].shape == (2, 3) and sum(v.nbytes for v in a.values()) < 64e6
+    # warm-up step = requests 0-1, timed steps = requests 2-3 and 4-5: the last step is dumped
+    assert a["request_index"].tolist() == [4.0, 5.0]
+    assert a["query_crc32"].tolist() == _stream_crcs(block=3)  # the rows' results carry those requests' queries
+    assert (a["output_tokens"] == 3).all() and (a["output_ids"] >= 0).all() and (a["prompt_tokens"] > 0).all()
+    for n in names:
+        assert np.array_equal(a[n], b[n]), n
+
+
+def test_bench_dump_outputs_continuous(tmp_path):
+    """Continuous mode (one warm-up step, two timed): the dump holds requests 4-5 of the stream,
+    the last timed step's, whatever order the closed loop completed them in."""
+    import numpy as np
+
+    d = _run(["--steps", "2", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 2
+    assert np.load(tmp_path / "request_index.npy").tolist() == [4.0, 5.0]
+    assert np.load(tmp_path / "query_crc32.npy").tolist() == _stream_crcs(block=3)
+    ids, scores = np.load(tmp_path / "output_ids.npy"), np.load(tmp_path / "evidence_scores.npy")
+    assert ids.shape == (2, 3) and (ids >= 0).all() and scores.shape[0] == 2 and (scores[:, 0] > 0).all()
+
+
+def test_bench_dump_outputs_refused_via_http(tmp_path):
+    """--via-http runs the servers as child processes: there is no in-process result to write,
+    so the combination is refused before anything starts."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--via-http", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120, cwd="/tmp")
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "d").exists()
+
+
 def test_bench_two_rank_dp():
     d = _run([], nproc=2)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 4

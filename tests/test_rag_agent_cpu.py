@@ -21,7 +21,8 @@ from llm_kubernetes_minikube_sharp4dev_amd.rag.index import RagHit, RagIndex, co
 
 # the reference knowledge base, shipped byte-for-byte (Minimal_RAG/knowledge/runbook_scaling.md:1-28)
 RUNBOOK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "knowledge", "runbook_scaling.md")
-REF_RUNBOOK = "/root/reference/Minimal_Agent_RAG/Minimal_RAG/knowledge/runbook_scaling.md"
+# size and SHA-256 of the reference's file, recorded once (the reference checkout is not needed)
+RUNBOOK_DIGEST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "runbook_scaling.digest.json")
 
 
 def test_reference_runbook_split_lengths():
@@ -33,9 +34,12 @@ def test_reference_runbook_split_lengths():
     assert extract_allowed_namespaces(secs[1]) == []
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RUNBOOK), reason="reference checkout not mounted")
 def test_shipped_runbook_is_the_reference_file():
-    assert open(RUNBOOK, "rb").read() == open(REF_RUNBOOK, "rb").read()
+    import hashlib
+
+    want = json.load(open(RUNBOOK_DIGEST))
+    data = open(RUNBOOK, "rb").read()
+    assert len(data) == want["bytes"] and hashlib.sha256(data).hexdigest() == want["sha256"]
 
 
 def test_knowledge_folder_index_has_the_reference_chunks():
@@ -273,10 +277,11 @@ def _tiny_stack():
     return tok, idx, eng, FakeCluster.default(), Config()
 
 
-@pytest.mark.parametrize("mode", ["inline", "threaded", "deferred"])
+@pytest.mark.parametrize("mode", ["inline", "threaded", "deferred", "stepped"])
 def test_continuous_load_rag_agent_mixed(mode):
     """Closed-loop continuous batching over the three workloads of bench.py (configs 2/3/5),
-    admission planned inline, on the planner thread, or launched and admitted once landed."""
+    admission planned inline, on the planner thread, launched and admitted once landed, or
+    launched and admitted one loop iteration later (stepped)."""
     from llm_kubernetes_minikube_sharp4dev_amd.agent.agent_pipeline import AgentPipeline, MixedPipeline
     from llm_kubernetes_minikube_sharp4dev_amd.agent.rag_pipeline import ContinuousLoad, RagAgentPipeline
     from llm_kubernetes_minikube_sharp4dev_amd.engine.sampling import SamplingParams
@@ -294,7 +299,7 @@ def test_continuous_load_rag_agent_mixed(mode):
     params = SamplingParams.greedy(4, ignore_eos=True)
     for pipe in (rag, agent, MixedPipeline(rag, agent)):
         load = ContinuousLoad(pipe, nq, params, concurrency=4, admit_chunk=2, threaded=mode == "threaded",
-                              deferred=mode == "deferred")
+                              deferred=mode in ("deferred", "stepped"), stepped=mode == "stepped")
         out = load.run(6)
         out += load.run(3)  # continues the same stream
         load.drain()
@@ -302,6 +307,39 @@ def test_continuous_load_rag_agent_mixed(mode):
         assert all(r.status in (200, 400, 404, 500) for r in out)
         assert all(r.output_tokens in (0, 4) for r in out)
         assert not eng.has_work()
+
+
+def test_stepped_admission_does_not_depend_on_when_the_topk_lands(monkeypatch):
+    """``ContinuousLoad(deferred=True, stepped=True)`` admits a launched retrieval one loop
+    iteration after its launch whether or not a poll would have found its top-k landed, so the
+    engine launch that first holds each request is the same when ``plan_ready`` always says yes
+    and when it always says no, and ``plan_ready`` is never asked.  The polled default asks it."""
+    from llm_kubernetes_minikube_sharp4dev_amd.agent.rag_pipeline import ContinuousLoad, RagAgentPipeline
+    from llm_kubernetes_minikube_sharp4dev_amd.engine.sampling import SamplingParams
+    from llm_kubernetes_minikube_sharp4dev_amd.rag.synthetic import make_queries
+
+    def admissions(stepped, ready):
+        tok, idx, eng, k8s, cfg = _tiny_stack()
+        rag = RagAgentPipeline(idx, eng, tok, k8s, cfg)
+        polls = []
+        monkeypatch.setattr(rag, "plan_ready", lambda h: polls.append(1) or ready)
+        stream = iter(make_queries(64, seed=1))
+        at, add = [], eng.add_request
+
+        def add_request(ids, params):
+            at.append(eng.launches)  # engine launches so far when the request is admitted
+            return add(ids, params)
+
+        monkeypatch.setattr(eng, "add_request", add_request)
+        load = ContinuousLoad(rag, lambda k: [next(stream) for _ in range(k)], SamplingParams.greedy(4, ignore_eos=True),
+                              concurrency=4, admit_chunk=2, deferred=True, stepped=stepped)
+        out = load.run(10)
+        load.drain()
+        return at[:10], [r.raw for r in out[:10]], len(polls)
+
+    yes, no = admissions(True, True), admissions(True, False)
+    assert yes == no and yes[2] == 0 and len(yes[0]) == 10
+    assert admissions(False, True)[2] > 0
 
 
 def test_sharded_search_keeps_the_local_exact_policy():
