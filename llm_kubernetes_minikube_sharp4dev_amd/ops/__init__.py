@@ -200,8 +200,8 @@ def flash_prefill(q, k, v, cu_q, Hq: int, Hkv: int, D: int, scale: float, causal
     """Varlen flash attention.  Paged when ``block_tables`` is given (K/V caches
     ``[NB, Hkv, BS, D]``), else dense K/V rows ``[T, >=Hkv*D]`` (encoder).
     ``part`` = (o f32 [T, Hq, D], ml f32 [T, Hq, 2]): write unnormalised partials for a
-    cascade / context-parallel merge instead of ``out`` (GPU only; ml = (running max, sum) in
-    the log2 domain).  ``q_past`` (int32 [B], GPU only): position of each sequence's first
+    cascade / context-parallel merge instead of ``out`` (ml = (running max, sum) in
+    the log2 domain).  ``q_past`` (int32 [B]): position of each sequence's first
     query relative to its first key for the causal mask (a context-parallel key shard), instead
     of ctx_len - q_len.
 
@@ -231,9 +231,14 @@ def flash_prefill(q, k, v, cu_q, Hq: int, Hkv: int, D: int, scale: float, causal
             return out
         return lib().flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, tiles[0], tiles[1], Hq,
                                    Hkv, D, scale, causal, out, pp_o, pp_ml, q_past)
-    if q_past is not None:
-        raise NotImplementedError("q_past: GPU kernel only")
-    y = ref.flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, causal)
+    if part is not None:
+        o, m, l = ref.flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, causal,
+                                    q_past=q_past, partials=True)
+        T = q.shape[0]
+        part[0].view(-1)[: T * Hq * D].copy_(o.reshape(-1))
+        part[1].view(-1)[: T * Hq * 2].copy_(torch.stack((m, l), dim=-1).reshape(-1))
+        return part[0]
+    y = ref.flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, causal, q_past=q_past)
     if out is not None:
         out[:, : Hq * D].copy_(y)
         return out

@@ -166,10 +166,44 @@ def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale):
     return out
 
 
-def flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, causal):
-    """q [T, >=Hq*D]; paged (block_tables given) or dense k/v [T, >=Hkv*D]."""
+def attention_partials(q, k, v, causal, past=0, scale=None):
+    """Unnormalised attention of q [Sq, Hq, D] over k/v [Sk, Hkv, D] in the format of the flash
+    kernel's partial mode: (o f32 [Sq, Hq, D] = sum_j 2^(s_j - m) v_j, m f32 [Sq, Hq] = the row
+    max of the scores in the log2 domain, l f32 [Sq, Hq] = sum_j 2^(s_j - m)).  A row that sees
+    no key (``past`` may be negative) has o = 0, m = -inf, l = 0."""
+    Sq, Hq, D = q.shape
+    Sk, Hkv, _ = k.shape
+    g = Hq // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    kf = k.double().repeat_interleave(g, dim=1)
+    vf = v.double().repeat_interleave(g, dim=1)
+    s = torch.einsum("qhd,khd->hqk", q.double(), kf) * (scale * 1.4426950408889634)
+    if causal:
+        qpos = past + torch.arange(Sq, device=q.device)[:, None]
+        kpos = torch.arange(Sk, device=q.device)[None, :]
+        s = s.masked_fill((kpos > qpos)[None], float("-inf"))
+    if Sk:
+        m = s.amax(dim=-1)
+    else:
+        m = torch.full((Hq, Sq), float("-inf"), dtype=torch.float64, device=q.device)
+    p = torch.exp2(s - torch.where(torch.isinf(m), torch.zeros_like(m), m)[..., None])
+    o = torch.einsum("hqk,khd->qhd", p, vf)
+    return o.float(), m.T.float(), p.sum(dim=-1).T.float()
+
+
+def flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, causal, q_past=None,
+                  partials=False):
+    """q [T, >=Hq*D]; paged (block_tables given) or dense k/v [T, >=Hkv*D].  ``q_past`` [B]:
+    position of each sequence's first query relative to its first key for the causal mask
+    (default ctx_len - q_len).  ``partials``: return the unnormalised (o f32 [T, Hq, D],
+    m f32 [T, Hq], l f32 [T, Hq]) of :func:`attention_partials` instead of the bf16 output,
+    whose rows without a visible key are zero."""
     T = q.shape[0]
-    out = torch.empty(T, Hq * D, dtype=q.dtype, device=q.device)
+    out = torch.zeros(T, Hq * D, dtype=q.dtype, device=q.device)
+    if partials:
+        po = torch.zeros(T, Hq, D, dtype=torch.float32, device=q.device)
+        pm = torch.full((T, Hq), float("-inf"), dtype=torch.float32, device=q.device)
+        pl = torch.zeros(T, Hq, dtype=torch.float32, device=q.device)
     cu = [int(x) for x in cu_q]
     for b in range(len(cu) - 1):
         s, e = cu[b], cu[b + 1]
@@ -184,9 +218,17 @@ def flash_prefill(q, k, v, block_tables, cu_q, ctx_lens, Hq, Hkv, D, scale, caus
             n = e - s
             kb = k[s:e, : Hkv * D].reshape(n, Hkv, D)
             vb = v[s:e, : Hkv * D].reshape(n, Hkv, D)
-        o = attention_ref(qb, kb, vb, causal, past=n - (e - s), scale=scale)
+        past = int(q_past[b]) if q_past is not None else n - (e - s)
+        if partials or q_past is not None:
+            o, m, l = attention_partials(qb, kb, vb, causal, past=past, scale=scale)
+            if partials:
+                po[s:e], pm[s:e], pl[s:e] = o, m, l
+                continue
+            o = o / l.clamp_min(1e-30)[..., None]  # rows without a visible key: 0 / tiny = 0
+        else:
+            o = attention_ref(qb, kb, vb, causal, past=past, scale=scale)
         out[s:e] = o.reshape(e - s, Hq * D).to(q.dtype)
-    return out
+    return (po, pm, pl) if partials else out
 
 
 def cosine_scores(corpus, cnorm, queries, qnorm, eps=1e-9):
