@@ -157,6 +157,27 @@ def case_knn(N=485_000, D=768, nq=64):
             "GB/s": N * D * 2 / t / 1e9}
 
 
+def case_logprobs(R=128, n=20, V=128256):
+    """Token log-probabilities of R requesting rows (bf16 logits as the LM head wrote them),
+    beside ops.sample (Ollama defaults) on the same shape in f32 as the yardstick."""
+    import numpy as np
+
+    logits = (torch.randn(R, V, device=DEV) * 3).to(torch.bfloat16)
+    ids = torch.randint(0, V, (R,), dtype=torch.int32, device=DEV)
+    rows = torch.arange(R, dtype=torch.int32, device=DEV)
+    t = timeit(lambda: ops.token_logprobs(logits, ids, rows, n))
+    prm = np.zeros((R, 8), dtype=np.int32)
+    prm.view(np.float32)[:, 0:3] = (0.8, 0.9, 1.1)
+    prm[:, 3], prm[:, 4], prm[:, 5], prm[:, 7] = 40, 64, np.arange(R), np.arange(R)
+    prm_t = torch.from_numpy(prm).to(DEV)
+    f32 = logits.float()
+    hist = torch.zeros(R, 256, dtype=torch.int32, device=DEV)
+    hl = torch.zeros(R, dtype=torch.int32, device=DEV)
+    ts = timeit(lambda: ops.sample(f32, prm_t, hist, hl, seed=1))
+    return {"case": f"token_logprobs R{R} V{V} bf16 n{n}", "us": t * 1e6, "GB/s": R * V * 2 / t / 1e9,
+            "sample_us": ts * 1e6}
+
+
 def case_gemm(M, N, K, layout="NT"):
     """hipBLASLt via torch: NT = x @ W^T with W [N,K] (nn.Linear layout), NN = x @ W with W [K,N]."""
     a = torch.randn(M, K, device=DEV, dtype=torch.bfloat16)
@@ -272,6 +293,7 @@ CASES = {
     "ln": lambda: [case_layernorm(), case_layernorm(8192), case_layernorm(32768, 384), case_layernorm(4096, 1024)],
     "norm": lambda: [case_rmsnorm(), case_silu(), case_silu(3584), case_silu(4096), case_silu(128), case_silu(4096, 1792),
                      case_silu_down(3584), case_silu_down(4096)],
+    "logprobs": lambda: [case_logprobs(R, n) for R in (1, 128) for n in (0, 20)],
     "knn": lambda: [case_knn(), case_knn(nq=8), case_knn(N=1_000_000, nq=8), case_knn(N=1_000_000, nq=128)],
     "gemm": lambda: [case_gemm(64, 6144, 4096), case_gemm(64, 28672, 4096), case_gemm(64, 4096, 14336),
                      case_gemm(32768, 6144, 4096), case_gemm(32768, 28672, 4096), case_gemm(32768, 4096, 14336)],

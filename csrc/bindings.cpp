@@ -930,6 +930,27 @@ at::Tensor sample(at::Tensor& logits, const at::Tensor& prm, at::Tensor& hist, a
   return out;
 }
 
+// Token log-probabilities of the requesting rows (csrc/sampling.hip lk_token_logprobs): see kernels.h
+std::vector<at::Tensor> token_logprobs(const at::Tensor& logits, const at::Tensor& ids, const at::Tensor& rows, int64_t n) {
+  CHECK_CUDA(logits); CHECK_LASTDIM(logits); CHECK_CUDA(ids); CHECK_I32(ids); CHECK_CONTIG(ids);
+  CHECK_CUDA(rows); CHECK_I32(rows); CHECK_CONTIG(rows);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "logits [B, V]");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or f32");
+  TORCH_CHECK(logits.size(1) < (1ll << 31) && logits.stride(0) >= logits.size(1), "logits row stride");
+  const int B = logits.size(0), V = logits.size(1), R = rows.numel();
+  TORCH_CHECK(ids.dim() == 1 && ids.numel() >= B, "ids [B]");
+  TORCH_CHECK(rows.dim() == 1, "rows [R]");
+  const int64_t ne = std::min<int64_t>(std::max<int64_t>(n, 0), std::min<int64_t>(20, V));
+  at::Tensor chosen = at::empty({R}, logits.options().dtype(at::kFloat));
+  at::Tensor top_lp = at::empty({R, ne}, logits.options().dtype(at::kFloat));
+  at::Tensor top_id = at::empty({R, ne}, logits.options().dtype(at::kInt));
+  int rc = lk_token_logprobs(logits.data_ptr(), is_bf16 ? 1 : 0, logits.stride(0), B, V, ip(rows), R, ip(ids), (int)std::min<int64_t>(std::max<int64_t>(n, -1), 1000),
+                             chosen.data_ptr<float>(), top_lp.data_ptr<float>(), top_id.data_ptr<int>(), cur_stream());
+  CHECK_RC(rc, "token_logprobs");
+  return {chosen, top_lp, top_id};
+}
+
 void repeat_penalty_(at::Tensor& logits, const at::Tensor& window, const at::Tensor& penalty) {
   CHECK_CUDA(logits); CHECK_I32(window); CHECK_F32(penalty); CHECK_CONTIG(window);
   const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
@@ -1193,6 +1214,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed") = 0, py::arg("step") = 0);
   m.def("select_tokens", &select_tokens, "", py::arg("logits"), py::arg("temps") = py::none(), py::arg("seed") = 0, py::arg("step") = 0, py::arg("out") = py::none());
   m.def("repeat_penalty_", &repeat_penalty_);
+  m.def("token_logprobs", &token_logprobs, "", py::arg("logits"), py::arg("ids"), py::arg("rows"), py::arg("n"));
   m.def("sample", &sample, "", py::arg("logits"), py::arg("prm"), py::arg("hist"), py::arg("hist_len"),
         py::arg("seed") = 0, py::arg("out") = py::none());
 }

@@ -204,6 +204,13 @@ int lk_repeat_penalty(void* logits, int is_bf16, long ls, int B, const int* wind
 // logits (f32, modified in place by the penalty) -> out int32 [B]; the token is appended to the ring.
 int lk_sample(float* logits, long ls, int B, int V, const int* prm, int* hist, int* hist_len, int W,
               unsigned long long seed, int* out, hipStream_t st);
+// Token log-probabilities: for each requesting batch row rows[r] (R of them, each in [0, B)),
+// log softmax of its logits (bf16 or f32, row stride ls >= V, read only) at ids[rows[r]] ->
+// chosen_lp f32 [R], and at the n' = min(n, V) most likely ids ordered by (value desc, id asc)
+// -> top_lp f32 [R, n'], top_id int32 [R, n'].  0 <= n <= 20, else -1; R == 0 launches nothing.
+// Rows that are not 16-byte aligned (ls % 8 != 0) are scanned element by element.
+int lk_token_logprobs(const void* logits, int is_bf16, long ls, int B, int V, const int* rows, int R,
+                      const int* ids, int n, float* chosen_lp, float* top_lp, int* top_id, hipStream_t st);
 
 // csrc/marker.hip: a one-wave marker kernel bounding a timed window in kernel traces
 int lk_window_mark(int id, hipStream_t st);

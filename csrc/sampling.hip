@@ -477,3 +477,247 @@ int lk_sample(float* logits, long ls, int B, int V, const int* prm, int* hist, i
   sample_topkp_kernel<<<B, kSampThreads, 0, st>>>(logits, ls, V, prm, hist, hist_len, W, seed, out);
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// Token log-probabilities (OpenAI / Ollama `logprobs`, `top_logprobs`): for each requesting
+// batch row, log softmax of the row's logits AS THE LM HEAD WROTE THEM at the chosen id and
+// at the n <= 20 most likely ids, ordered like the sampler orders (value desc, id asc).
+// One workgroup of 1024 threads per requesting row, bf16 rows read as bf16:
+//   1. one pass with 16-byte loads: each thread keeps an online (max, sum exp(x - max)) pair
+//      and the largest key of its elements; a butterfly + 16-wave combine gives the row
+//      maximum and log-sum-exp (exponents are only ever taken of x - a running maximum);
+//   2. the n-th largest of the 1024 per-thread maxima bounds the n-th largest value from
+//      below; a second pass appends every element >= it to an LDS candidate list (about n
+//      of them; a plateau of more than kLpCand -> the sampler's exact 3-digit radix select
+//      for the n-th key, then the strictly larger keys plus the lowest-index ties);
+//   3. bitonic sort of the candidates; the first n are the answer.  -inf entries take part
+//      (logprob -inf, after every finite value).
+// Keys are compared on the loaded values themselves; the logits are never written.
+constexpr int kLpMaxN = 20, kLpCand = 2048;
+static_assert(kLpCand >= kSampThreads && kLpCand >= 2048, "thread maxima and the radix histogram live in ckey");
+
+// f(value, index) for each element of the row this thread owns: 8-element chunks strided over
+// the workgroup plus a scalar tail (VEC: 16-byte-aligned rows), or a plain strided scan
+template <bool BF16, bool VEC, class F>
+LK_DEVICE void lp_scan_row(const void* rowp, int V, F&& f) {
+  const int tid = threadIdx.x;
+  const int nv = VEC ? V / 8 : 0;
+  if constexpr (BF16) {
+    const bf16_t* lp = reinterpret_cast<const bf16_t*>(rowp);
+    for (int c = tid; c < nv; c += kSampThreads) {
+      float v[8];
+      load8(lp + c * 8, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f(v[j], c * 8 + j);
+    }
+    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(bf2f(lp[i]), i);
+  } else {
+    const float* lp = reinterpret_cast<const float*>(rowp);
+    for (int c = tid; c < nv; c += kSampThreads) {
+      const float4 a = *reinterpret_cast<const float4*>(lp + c * 8);
+      const float4 b = *reinterpret_cast<const float4*>(lp + c * 8 + 4);
+      f(a.x, c * 8 + 0); f(a.y, c * 8 + 1); f(a.z, c * 8 + 2); f(a.w, c * 8 + 3);
+      f(b.x, c * 8 + 4); f(b.y, c * 8 + 5); f(b.z, c * 8 + 6); f(b.w, c * 8 + 7);
+    }
+    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(lp[i], i);
+  }
+}
+
+// block-wide inclusive scan of counts (1024 threads = 16 waves)
+LK_DEVICE int block_scan_i(int v, int* wsum) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  __syncthreads();
+  if (lane == 63) wsum[w] = v;
+  __syncthreads();
+  int add = 0;
+  for (int i = 0; i < w; ++i) add += wsum[i];
+  return v + add;
+}
+
+// (max, sum exp(x - max)) of two partial rows; an empty part is (-FLT_MAX, 0)
+LK_DEVICE void lse_merge(float& m, float& s, float m2, float s2) {
+  const float mn = fmaxf(m, m2);
+  s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
+  m = mn;
+}
+
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void* __restrict__ logits, long ls, int B, int V,
+                                                                     const int* __restrict__ rows,
+                                                                     const int* __restrict__ ids, int n,
+                                                                     float* __restrict__ chosen_lp,
+                                                                     float* __restrict__ top_lp,
+                                                                     int* __restrict__ top_id) {
+  __shared__ unsigned ckey[kLpCand];
+  __shared__ int cidx[kLpCand];
+  __shared__ float wm[16], ws[16];
+  __shared__ int iw[16];
+  __shared__ int ncand_s, thr_s, above_s;
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int row = rows[r];
+  if (row < 0 || row >= B) {  // uniform per workgroup: a row outside the batch is never read
+    if (tid == 0) chosen_lp[r] = __uint_as_float(0x7FC00000u);
+    if (tid < n) {
+      top_lp[(long)r * n + tid] = __uint_as_float(0x7FC00000u);
+      top_id[(long)r * n + tid] = -1;
+    }
+    return;
+  }
+  const void* rowp = BF16 ? (const void*)(reinterpret_cast<const bf16_t*>(logits) + (long)row * ls)
+                          : (const void*)(reinterpret_cast<const float*>(logits) + (long)row * ls);
+  auto at = [&](int i) -> float {
+    if constexpr (BF16) return bf2f(reinterpret_cast<const bf16_t*>(rowp)[i]);
+    else return reinterpret_cast<const float*>(rowp)[i];
+  };
+
+  // 1. online (max, sum exp) and the thread's largest key
+  float m = -3.402823466e+38f, s = 0.f;
+  unsigned tmax = 0;
+  lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int) {
+    const float mn = fmaxf(m, x);
+    s = s * __expf(m - mn) + __expf(x - mn);
+    m = mn;
+    tmax = max(tmax, fkey(x));
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_merge(m, s, m2, s2);
+  }
+  if (lane == 0) {
+    wm[w] = m;
+    ws[w] = s;
+  }
+  ckey[tid] = tmax;
+  cidx[tid] = tid;
+  if (tid == 0) ncand_s = 0;
+  __syncthreads();
+  m = wm[0];
+  s = ws[0];
+  for (int j = 1; j < 16; ++j) lse_merge(m, s, wm[j], ws[j]);  // the same order in every thread
+  const float rowmax = m, logsum = logf(s);
+  if (tid == 0) {
+    const int id = ids[row];
+    chosen_lp[r] = (id >= 0 && id < V) ? (at(id) - rowmax) - logsum : __uint_as_float(0x7FC00000u);
+  }
+  if (n == 0) return;  // uniform
+
+  // 2. lower bound of the n-th largest value, then every element >= it
+  bitonic(ckey, cidx, kSampThreads);
+  const unsigned t0 = ckey[n - 1];  // threads without elements hold key 0: a short row gathers whole
+  __syncthreads();
+  lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
+    const unsigned k = fkey(x);
+    if (k >= t0) {
+      const int p = atomicAdd(&ncand_s, 1);
+      if (p < kLpCand) {
+        ckey[p] = k;
+        cidx[p] = i;
+      }
+    }
+  });
+  __syncthreads();
+  int nc = ncand_s;
+  if (nc > kLpCand) {
+    // a plateau at or above the bound: the exact n-th key by a 3-digit MSB radix select over LDS
+    // histograms (sample_topkp_kernel's scheme, -inf entries included), then gather
+    unsigned* hst = ckey;  // 2048 bins
+    unsigned prefix = 0, mask = 0;
+    int kr = n;
+    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
+    for (int d = 0; d < 3; ++d) {
+      const int nb = 1 << bits[d];
+      for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
+      __syncthreads();
+      lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int) {
+        const unsigned k = fkey(x);
+        if ((k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
+      });
+      __syncthreads();
+      // thread t owns bins 2047 - 2t and 2046 - 2t: the scan runs from the top bin down
+      const int hi = 2047 - 2 * tid;
+      const int c_hi = hi < nb ? (int)hst[hi] : 0, c_lo = hi - 1 < nb ? (int)hst[hi - 1] : 0;
+      const int incl = block_scan_i(c_hi + c_lo, iw);
+      const int excl = incl - (c_hi + c_lo);
+      if (excl < kr && incl >= kr) {
+        const int b = (excl + c_hi >= kr) ? hi : hi - 1;
+        thr_s = b;
+        above_s = excl + (b == hi ? 0 : c_hi);  // elements strictly above bin b
+      }
+      __syncthreads();
+      kr -= above_s;
+      prefix |= (unsigned)thr_s << shifts[d];
+      mask |= (unsigned)(nb - 1) << shifts[d];
+      __syncthreads();
+    }
+    // keys > prefix (n - kr of them, fewer than n), then the first kr ties in index order
+    if (tid == 0) ncand_s = 0;
+    __syncthreads();
+    lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
+      const unsigned k = fkey(x);
+      if (k > prefix) {
+        const int p = atomicAdd(&ncand_s, 1);
+        if (p < kLpCand) {
+          ckey[p] = k;
+          cidx[p] = i;
+        }
+      }
+    });
+    __syncthreads();
+    int base = ncand_s, need = kr;
+    for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
+      const int i = c0 + tid;
+      const bool tie = i < V && fkey(at(i)) == prefix;
+      const int pos = block_scan_i(tie ? 1 : 0, iw);  // ties up to and including this thread
+      if (tie && pos <= need) {
+        ckey[base + pos - 1] = prefix;
+        cidx[base + pos - 1] = i;
+      }
+      if (tid == kSampThreads - 1) thr_s = pos;  // ties in this chunk
+      __syncthreads();
+      const int taken = min(need, thr_s);
+      base += taken;
+      need -= taken;
+      __syncthreads();
+    }
+    nc = base;
+  }
+  // 3. sort the candidates; the first n are the top n
+  int n2 = 1;
+  while (n2 < nc) n2 <<= 1;
+  for (int i = nc + tid; i < n2; i += kSampThreads) {
+    ckey[i] = 0;
+    cidx[i] = 0x7fffffff;
+  }
+  __syncthreads();
+  bitonic(ckey, cidx, n2);
+  if (tid < n) {
+    const bool ok = tid < nc;  // always: the row has at least n elements
+    top_lp[(long)r * n + tid] = ok ? (keyf(ckey[tid]) - rowmax) - logsum : __uint_as_float(0x7FC00000u);
+    top_id[(long)r * n + tid] = ok ? cidx[tid] : -1;
+  }
+}
+
+int lk_token_logprobs(const void* logits, int is_bf16, long ls, int B, int V, const int* rows, int R,
+                      const int* ids, int n, float* chosen_lp, float* top_lp, int* top_id, hipStream_t st) {
+  if (n < 0 || n > kLpMaxN) return -1;
+  if (R <= 0) return 0;
+  if (B < 1 || V < 1 || ls < V) return -1;
+  if (n > V) n = V;
+  // 16-byte loads need 16-byte-aligned rows; any other layout is scanned element by element
+  const bool vec = ls % 8 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+  if (is_bf16) {
+    if (vec) token_logprobs_kernel<true, true><<<R, kSampThreads, 0, st>>>(logits, ls, B, V, rows, ids, n, chosen_lp, top_lp, top_id);
+    else token_logprobs_kernel<true, false><<<R, kSampThreads, 0, st>>>(logits, ls, B, V, rows, ids, n, chosen_lp, top_lp, top_id);
+  } else {
+    if (vec) token_logprobs_kernel<false, true><<<R, kSampThreads, 0, st>>>(logits, ls, B, V, rows, ids, n, chosen_lp, top_lp, top_id);
+    else token_logprobs_kernel<false, false><<<R, kSampThreads, 0, st>>>(logits, ls, B, V, rows, ids, n, chosen_lp, top_lp, top_id);
+  }
+  LK_CHECK_LAUNCH();
+  return 0;
+}

@@ -25,7 +25,9 @@ log = get_logger("engine")
 
 
 def _plain_greedy(p: SamplingParams) -> bool:
-    return p.is_greedy and p.logits_processor is None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
+    # (a request for log-probabilities needs the step's logits: the sampler's logits path)
+    return (p.is_greedy and p.logits_processor is None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
+            and not p.logprobs)
 
 
 # order of the pipelined step's phases: "csl" (default) collect -> sample -> launch, or the
@@ -44,8 +46,10 @@ GEMM_HEALTH_EVERY = int(os.environ.get("LK_GEMM_HEALTH_EVERY", "512"))
 def _jump_ok(p: SamplingParams) -> bool:
     """Forced tokens can be appended without sampling: a grammar is set, and no repeat
     penalty reads the device history ring the sampler kernel appends to (host-appended
-    tokens would be missing from it)."""
-    return p.logits_processor is not None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
+    tokens would be missing from it), and no log-probabilities are asked for (a host-appended
+    token has no logits row of its own to take them from)."""
+    return (p.logits_processor is not None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
+            and not p.logprobs)
 
 
 def _small_buckets() -> tuple:
@@ -231,14 +235,24 @@ class LLMEngine:
     def _sample(self, launched):
         batch, rows, out, greedy, ts, t0, t1, ev0n = launched
         ev0 = ev0n[0]
-        host = ev = ids = None
+        host = ev = ids = lps = None
         if rows:
             seqs = [s for s, _ in rows]
             ids = out if greedy else self.sampler(out, [s.params for s in seqs], [s.output_ids for s in seqs],
                                                   [s.req_id for s in seqs])
+            # (a plain-greedy step has no requesting row: _plain_greedy)
+            lps = None if greedy else self.sampler.last_logprobs
             if ids.is_cuda:
                 host = torch.empty(ids.shape, dtype=ids.dtype, pin_memory=True)
                 host.copy_(ids, non_blocking=True)
+                if lps is not None:
+                    # the log-probabilities ride to pinned memory under the same event as the ids
+                    staged = []
+                    for t in lps[2:]:
+                        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                        h.copy_(t, non_blocking=True)
+                        staged.append(h)
+                    lps = lps[:2] + tuple(staged)
                 ev = torch.cuda.Event(enable_timing=ev0 is not None)
                 ev.record()
                 self._last_ids_ev = ev
@@ -254,10 +268,10 @@ class LLMEngine:
             # still bounds the traced GPU time, so the next step's idle is not charged with it
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
-        return (batch, rows, host, ev, ts, t0, t1, time.perf_counter(), ev0n)
+        return (batch, rows, host, ev, ts, t0, t1, time.perf_counter(), ev0n, lps)
 
     def _collect(self, pending) -> list:
-        batch, rows, host, ev, ts, t0, t1, t1s, (ev0, launched_note, starved) = pending
+        batch, rows, host, ev, ts, t0, t1, t1s, (ev0, launched_note, starved), lps = pending
         t2 = time.perf_counter()
         if rows and ev is not None:
             ev.synchronize()  # outside the lock: aborts and admissions never wait on the device
@@ -266,7 +280,8 @@ class LLMEngine:
             if rows:
                 ids = host.tolist()
                 now = t2 = time.perf_counter()
-                for (seq, _), tid in zip(rows, ids):
+                lp_of = self._logprob_entries(rows, lps) if lps is not None else None
+                for i, ((seq, _), tid) in enumerate(zip(rows, ids)):
                     if seq.discard_rows:
                         # the row predicted a token jump-forward appended meanwhile: its KV
                         # write (the previous token) is what the step was for
@@ -275,7 +290,7 @@ class LLMEngine:
                     seq.num_inflight, seq.inflight_row = 0, -1
                     if seq.finished:
                         continue  # aborted, or stopped while this step was in flight
-                    self._append(seq, int(tid), now)
+                    self._append(seq, int(tid), now, lp_of.get(i) if lp_of else None)
                     if JUMP_FORWARD and not seq.finished and _jump_ok(seq.params):
                         self._jump(seq, now)
                     out.append(seq)
@@ -321,6 +336,18 @@ class LLMEngine:
             M.KV_USAGE.set(self.allocator.usage())
             M.RUNNING.set(len(self.scheduler.running))
             return out
+
+    @staticmethod
+    def _logprob_entries(rows, lps) -> dict:
+        """batch row -> (chosen logprob, [(id, logprob), ...]) for the rows that asked, each list
+        cut to its own request's top_logprobs (the kernel ran with the largest of the step)."""
+        want, _, chosen, top_lp, top_id = lps
+        chosen, top_lp, top_id = chosen.tolist(), top_lp.tolist(), top_id.tolist()
+        out = {}
+        for r, i in enumerate(want):
+            k = max(int(rows[i][0].params.top_logprobs), 0)
+            out[i] = (chosen[r], list(zip(top_id[r][:k], top_lp[r][:k])))
+        return out
 
     @staticmethod
     def _check_gemm_health(device=None):
@@ -372,10 +399,12 @@ class LLMEngine:
             if inflight_kv:
                 seq.discard_rows += 1
 
-    def _append(self, seq: Sequence, tid: int, now: float):
+    def _append(self, seq: Sequence, tid: int, now: float, logprob=None):
         if seq.first_token_at is None:
             seq.first_token_at = now
         seq.output_ids.append(tid)
+        if logprob is not None:
+            seq.logprobs.append(logprob)  # before on_token: consumers read seq.logprobs[-1]
         p = seq.params
         reason = None
         n = len(seq.output_ids)

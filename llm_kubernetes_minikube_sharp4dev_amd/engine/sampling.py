@@ -36,6 +36,10 @@ class SamplingParams:
     ignore_eos: bool = False
     # callable(generated_ids) -> allowed token-id tensor/list or None (constrained decoding)
     logits_processor: Optional[Callable] = None
+    # token log-probabilities of the model's own distribution (docs/logprobs.md): the chosen
+    # token's, and the top_logprobs (0..20) most likely tokens' per generated token
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @classmethod
     def greedy(cls, max_tokens: int = 256, **kw) -> "SamplingParams":
@@ -198,9 +202,33 @@ class Sampler:
         lg = logits if logits.dtype == torch.float32 and logits.is_contiguous() else logits.float().contiguous()
         return ops.sample(lg, prm_t, hist, hist_len, seed)
 
+    # the last call's log-probabilities: None when no row asked, else (rows, n, chosen_lp [R],
+    # top_lp [R, n'], top_id [R, n']) -- the requesting batch rows in order, the largest
+    # top_logprobs among them, and ops.token_logprobs' tensors on the logits' device
+    last_logprobs = None
+
     def __call__(self, logits: torch.Tensor, params: list, histories: list, keys: Optional[list] = None) -> torch.Tensor:
-        """logits [B, V] (f32) -> int32 token ids [B] (on logits.device).  ``keys``: a stable
-        id per row's sequence (its history ring); default the row index."""
+        """logits [B, V] (f32 or bf16) -> int32 token ids [B] (on logits.device).  ``keys``: a
+        stable id per row's sequence (its history ring); default the row index.  When a row's
+        params ask for ``logprobs``, the logits are left untouched (mask and penalty work on
+        a private copy) and :attr:`last_logprobs` holds the result of one
+        ``ops.token_logprobs`` launch over the requesting rows; otherwise it is None and the
+        call is the one it always was (the logits may be edited in place)."""
+        want = [i for i, p in enumerate(params) if p.logprobs]
+        self.last_logprobs = None
+        if not want:
+            return self._choose(logits, params, histories, keys, False)
+        ids = self._choose(logits, params, histories, keys, True)
+        n = max(min(max(int(params[i].top_logprobs), 0), ops.ref.LOGPROBS_MAX_N) for i in want)
+        rows_t = torch.tensor(want, dtype=torch.int32)
+        if logits.device.type == "cuda":
+            rows_t = rows_t.pin_memory().to(logits.device, non_blocking=True)
+        ids32 = ids if ids.dtype == torch.int32 else ids.int()
+        self.last_logprobs = (want, n) + tuple(ops.token_logprobs(logits, ids32, rows_t, n))
+        return ids
+
+    def _choose(self, logits: torch.Tensor, params: list, histories: list, keys: Optional[list], keep: bool) -> torch.Tensor:
+        """Token ids of every row; ``keep``: the caller's logits must stay as they are."""
         self.step += 1
         B = logits.shape[0]
         dev = logits.device
@@ -224,7 +252,12 @@ class Sampler:
         if rows and not need_filter and not need_penalty and SPARSE_SELECT and ops.use_hip(logits):
             # selection straight over each row's allowed ids (HIP select_allowed): no mask
             plan = self._plan(rows, B, dev)
-        elif rows:
+        if keep and ((rows and plan is None) or need_filter or need_penalty):
+            # the dense mask and the penalty kernel edit their input: give them a private copy
+            # (the f32 copy the fused sampler would make of bf16 logits anyway, else a clone)
+            fused = need_filter or need_penalty
+            logits = logits.float().contiguous() if fused and logits.dtype != torch.float32 else logits.clone()
+        if plan is None and rows:
             crow = list(rows)
             flat = [rows[i] + j * V for j, i in enumerate(crow)]
             idx = torch.from_numpy(np.concatenate(flat)).to(dev, non_blocking=True)

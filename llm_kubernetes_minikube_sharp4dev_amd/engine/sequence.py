@@ -24,6 +24,9 @@ class Sequence:
     params: SamplingParams
     req_id: str = field(default_factory=lambda: f"req-{next(_ids)}")
     output_ids: list = field(default_factory=list)
+    # one (chosen logprob, [(token id, logprob), ...]) per output token when params.logprobs is
+    # set (len(logprobs) == len(output_ids) at all times), else empty
+    logprobs: list = field(default_factory=list)
     block_table: list = field(default_factory=list)
     num_computed: int = 0          # tokens whose K/V are in the cache
     num_cached_prefix: int = 0     # tokens served by the prefix cache at admission

@@ -22,7 +22,7 @@ __all__ = [
     "pool_normalize", "row_norms", "select_tokens", "repeat_penalty_", "sample", "linear", "linear_swiglu",
     "decode_splits", "rope_cos_sin", "argmax_key", "key_to_id", "tune_gemm", "tune_decode", "gemm", "linear_add_rmsnorm", "linear_rope_kv",
     "prefill_chain_ok", "linear_resid", "linear_qkv_fused", "linear_swiglu_scaled", "embed_rows", "scatter_ids",
-    "gather_rows",
+    "gather_rows", "token_logprobs",
 ]
 
 rope_cos_sin = ref.rope_cos_sin
@@ -317,6 +317,16 @@ def sample(logits, prm, hist, hist_len, seed: int = 0, out=None):
     if use_hip(logits):
         return lib().sample(logits, prm, hist, hist_len, int(seed) & ((1 << 63) - 1), out)
     return ref.sample(logits, prm, hist, hist_len, seed)
+
+
+def token_logprobs(logits, ids, rows, n: int):
+    """Log-probabilities of the just-selected tokens and of the ``n`` (0..20) most likely ones,
+    for the batch rows ``rows`` (int32 [R]) only: ``log_softmax`` of the logits as stored (bf16
+    or f32, never modified) -> (chosen_lp f32 [R], top_lp f32 [R, n'], top_id int32 [R, n']),
+    n' = min(n, V), the top lists ordered by (logit desc, id asc)."""
+    if use_hip(logits):
+        return tuple(lib().token_logprobs(logits, ids, rows, int(n)))
+    return ref.token_logprobs(logits, ids, rows, n)
 
 
 def repeat_penalty_(logits, window, penalty):

@@ -305,6 +305,26 @@ def keys_to_ids(keys):
     return ((~(k & 0xFFFFFFFF)) & 0xFFFFFFFF).int()
 
 
+LOGPROBS_MAX_N = 20  # csrc/sampling.hip kLpMaxN
+
+
+def token_logprobs(logits, ids, rows, n: int):
+    """fp32 reference of lk_token_logprobs (csrc/sampling.hip): for each requesting batch row
+    ``rows[r]``, ``log_softmax`` of its logits as stored at ``ids[rows[r]]`` -> chosen_lp f32
+    [R], and at the ``min(n, V)`` most likely ids ordered by (value desc, id asc) -> top_lp f32
+    [R, n'], top_id int32 [R, n'].  The logits are not modified."""
+    if not 0 <= int(n) <= LOGPROBS_MAX_N:
+        raise ValueError(f"token_logprobs: n must be in 0..{LOGPROBS_MAX_N}, got {n}")
+    V = logits.shape[1]
+    ne = min(int(n), V)
+    rows_l = rows.long()
+    x = logits.index_select(0, rows_l).float()
+    lp = torch.log_softmax(x, dim=-1)
+    chosen = lp.gather(1, ids.long().index_select(0, rows_l)[:, None]).squeeze(1)
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, :ne]
+    return chosen, lp.gather(1, order), order.int()
+
+
 def repeat_penalty_(logits, window, penalty):
     for b in range(logits.shape[0]):
         p = float(penalty[b])

@@ -11,6 +11,8 @@ with a compact binary protocol:
   client -> core  ["gen", rid, model, ids, sampling-dict, format] | ["abort", rid]
                   | ["embed", rid, model, texts] | ["load", rid, model]
   core -> client  ["tok", [[rid, [ids..], finished, reason, cached_prefix, error], ...], stats]
+                    (an item of a request that asked for logprobs has a 7th element: one
+                    [chosen logprob, [[id, logprob], ...]] entry per id of the item)
                   | ["emb", rid, f32 bytes, rows, dim] | ["load", rid, meta] | ["err", rid, msg]
 
 Every engine step's tokens for one connection leave as ONE frame (the engine thread appends
@@ -67,7 +69,10 @@ SP_FIELDS = ("temperature", "top_k", "top_p", "repeat_penalty", "repeat_last_n",
 
 
 def sp_to_wire(sp: SamplingParams) -> dict:
-    return {k: getattr(sp, k) for k in SP_FIELDS}
+    d = {k: getattr(sp, k) for k in SP_FIELDS}
+    if sp.logprobs:  # only when asked: every other request's frame is what it always was
+        d["logprobs"], d["top_logprobs"] = True, int(sp.top_logprobs)
+    return d
 
 
 def _accounting(seq) -> dict:
@@ -113,6 +118,9 @@ class _Conn:
         # a finished request carries its engine accounting (cached prefix, preemptions, steps)
         item = [rid, tid, fin, (seq.finish_reason or "stop") if fin else None,
                 _accounting(seq) if fin else None, getattr(seq, "error", None) if tid < 0 else None]
+        if seq.params.logprobs:
+            lp = seq.logprobs[-1] if tid >= 0 and seq.logprobs else None
+            item.append([lp[0], [[i, v] for i, v in lp[1]]] if lp is not None else None)
         with self.lock:
             self.pending.append(item)
         self.wake.set()
@@ -137,13 +145,15 @@ class _Conn:
                     # coalesce per request: [rid, [ids], fin, reason, cached, error]
                     by: dict = {}
                     order = []
-                    for rid, tid, fin, reason, cached, err in toks:
+                    for rid, tid, fin, reason, cached, err, *lp in toks:
                         e = by.get(rid)
                         if e is None:
-                            e = by[rid] = [rid, [], False, None, None, None]
+                            e = by[rid] = [rid, [], False, None, None, None] + ([[]] if lp else [])
                             order.append(rid)
                         if tid >= 0:
                             e[1].append(tid)
+                            if lp:
+                                e[6].append(lp[0])
                         if fin:
                             e[2], e[3], e[4], e[5] = True, reason, cached, err
                             self.reqs.pop(rid, None)

@@ -29,6 +29,7 @@ class FakeCore:
 
     async def _conn(self, reader, writer):
         active: dict = {}  # rid -> tokens left
+        want: dict = {}    # rid -> top_logprobs of a request that asked for logprobs
         lock = asyncio.Lock()
 
         def send(obj):
@@ -51,6 +52,10 @@ class FakeCore:
                     else:
                         active[rid] = left
                         items.append([rid, [tid], False, None, None, None])
+                    if rid in want:
+                        # the real core's 7th element: one [chosen, [[id, logprob], ...]] per id
+                        n = want[rid] if left > 0 else want.pop(rid)
+                        items[-1].append([[-0.5, [[tid + j, -0.5 - j] for j in range(n)]]])
                 send(["tok", items, [100000, 0, len(active)]])
                 await writer.drain()
 
@@ -63,7 +68,10 @@ class FakeCore:
                 if op == "gen":
                     sp = msg[4]
                     active[rid] = min(self.tokens, int(sp.get("max_tokens") or self.tokens))
+                    if sp.get("logprobs"):
+                        want[rid] = int(sp.get("top_logprobs") or 0)
                 elif op == "abort":
+                    want.pop(rid, None)
                     if active.pop(rid, None) is not None:
                         self.aborted += 1
                 elif op == "load":

@@ -25,6 +25,7 @@ from fastapi import Request  # module level: FastAPI resolves string annotations
 
 import asyncio
 import json
+import math
 import os
 import time
 import uuid
@@ -115,7 +116,54 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
 
             sp.format = fmt  # a remote engine core rebuilds the processor from the spec
             sp.logits_processor = json_logits_processor(h.tokenizer, fmt if isinstance(fmt, dict) else None)
+        # Ollama puts these at the request's top level, not in options
+        return set_logprobs(sp, bool(b.get("logprobs")), b.get("top_logprobs"))
+
+    # ---- token log-probabilities (docs/logprobs.md): request fields -> SamplingParams, engine
+    # entries (chosen logprob, [(id, logprob), ...]) -> OpenAI-shaped JSON entries
+    def set_logprobs(sp: SamplingParams, want, top) -> SamplingParams:
+        """``logprobs`` (bool) / ``top_logprobs`` (int 0..20) of a request's top level; raises
+        ValueError (-> 400) on a bad combination."""
+        if top is None:
+            top = 0
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= 20:
+            raise ValueError("top_logprobs must be an integer between 0 and 20")
+        if top > 0 and not want:
+            raise ValueError("top_logprobs requires logprobs to be true")
+        if want:
+            sp.logprobs, sp.top_logprobs = True, top
         return sp
+
+    def _lp_json(v) -> float:
+        return float(v) if v is not None and math.isfinite(v) else -9999.0  # JSON has no -inf
+
+    def lp_entry_maker(h):
+        tok = h.tokenizer
+        table = tok.token_bytes_table() if hasattr(tok, "token_bytes_table") else None
+
+        def tok_bytes(i: int) -> bytes:
+            if table is not None:
+                return table[i] if 0 <= i < len(table) else b""
+            return tok.piece(i).encode()
+
+        def one(i: int, lp) -> dict:
+            raw = tok_bytes(int(i))
+            return {"token": raw.decode("utf-8", errors="replace"), "logprob": _lp_json(lp), "bytes": list(raw)}
+
+        def entry(tid: int, lp) -> dict:
+            e = one(tid, lp[0])
+            e["top_logprobs"] = [one(i, v) for i, v in lp[1]]
+            return e
+
+        return entry
+
+    def lp_entries(h, seq) -> list:
+        """One entry per generated token of a finished request, a terminating EOS left out."""
+        entry = lp_entry_maker(h)
+        ids = list(seq.output_ids)
+        if ids and seq.finish_reason == "stop" and ids[-1] in h.engine.eos_ids:
+            ids = ids[:-1]
+        return [entry(t, lp) for t, lp in zip(ids, seq.logprobs)]
 
     def prompt_ids(h, prompt: str, system: Optional[str], raw: bool) -> list:
         tok = h.tokenizer
@@ -128,8 +176,11 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         t0 = time.perf_counter_ns()
         detok = IncrementalDetokenizer(h.tokenizer)
         stop_strs = [s for s in sp.stop if s]
+        lp_entry = lp_entry_maker(h) if sp.logprobs else None
 
         async def gen():
+            lps = []  # entries of the tokens consumed since the last chunk that carried them
+            ntok = 0
             text = ""
             seq = None
             first_ns = None
@@ -143,6 +194,11 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                     if first_ns is None:
                         first_ns = time.perf_counter_ns()
                     piece = detok.push(tid) if tid >= 0 and not (fin and tid in h.engine.eos_ids) else ""
+                    if lp_entry is not None and tid >= 0:
+                        # (s is live: index by the tokens consumed here, not by its current length)
+                        if not (fin and tid in h.engine.eos_ids) and ntok < len(s.logprobs):
+                            lps.append(lp_entry(tid, s.logprobs[ntok]))
+                        ntok += 1
                     text += piece
                     if stop_strs:
                         cut = min((text.find(st) for st in stop_strs if st in text), default=-1)
@@ -150,7 +206,10 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                             piece = piece[: max(0, len(piece) - (len(text) - cut))]
                             text = text[:cut]
                     if piece and stream:
-                        yield json.dumps(mk_chunk(piece), ensure_ascii=False) + "\n"
+                        ch = mk_chunk(piece)
+                        if lp_entry is not None:
+                            ch["logprobs"], lps = lps, []
+                        yield json.dumps(ch, ensure_ascii=False) + "\n"
                     emitted += 1
             except asyncio.TimeoutError:
                 yield json.dumps({"error": "request timed out"}) + ("\n" if stream else "")
@@ -185,6 +244,8 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                     if v is not None:
                         tracing.count("server", name, v)
             final = mk_final(text, reason, stats, ids + (seq.output_ids if seq else []))
+            if lp_entry is not None:
+                final["logprobs"] = lps  # streamed: the leftovers; else every entry
             yield json.dumps(final, ensure_ascii=False) + ("\n" if stream else "")
 
         if stream:
@@ -217,7 +278,10 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         ids = prompt_ids(h, prompt, b.get("system"), bool(b.get("raw")))
         if len(ids) >= h.engine.max_model_len:
             ids = ids[-(h.engine.max_model_len - 1):]  # Ollama truncates to num_ctx
-        sp = params_for(b, h)
+        try:
+            sp = params_for(b, h)
+        except ValueError as e:
+            return err(400, str(e))
         stream = b.get("stream", True) is not False
 
         def chunk(piece):
@@ -255,7 +319,10 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                                  "done": True, "done_reason": "load"})
         system, prompt = _chat_to_prompt(msgs)
         ids = prompt_ids(h, prompt, system, False)
-        sp = params_for(b, h)
+        try:
+            sp = params_for(b, h)
+        except ValueError as e:
+            return err(400, str(e))
         stream = b.get("stream", True) is not False
 
         def chunk(piece):
@@ -452,12 +519,18 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                 "stop": b.get("stop"), "num_predict": b.get("max_tokens") or -1}
         sp = SamplingParams.from_ollama({k: v for k, v in opts.items() if v is not None}, mgr.cfg.engine,
                                         mgr.cfg.engine.default_max_new_tokens)
+        try:
+            set_logprobs(sp, bool(b.get("logprobs")), b.get("top_logprobs"))
+        except ValueError as e:
+            return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
         seq = await h.async_engine.generate(ids, sp)
         text = h.tokenizer.decode(seq.output_ids)
         cid = "chatcmpl-" + uuid.uuid4().hex[:12]
+        choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": seq.finish_reason}
+        if sp.logprobs:
+            choice["logprobs"] = {"content": lp_entries(h, seq)}
         return {"id": cid, "object": "chat.completion", "created": int(time.time()), "model": model,
-                "choices": [{"index": 0, "message": {"role": "assistant", "content": text},
-                             "finish_reason": seq.finish_reason}],
+                "choices": [choice],
                 "usage": {"prompt_tokens": len(ids), "completion_tokens": len(seq.output_ids),
                           "total_tokens": len(ids) + len(seq.output_ids)}}
 
@@ -472,10 +545,28 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         ids = h.tokenizer.encode(b.get("prompt") or "", add_bos=True)
         sp = SamplingParams.from_ollama({"temperature": b.get("temperature", 1.0),
                                          "num_predict": b.get("max_tokens") or 16}, mgr.cfg.engine)
+        n_lp = b.get("logprobs")  # the legacy integer: the number of alternatives per token
+        try:
+            if isinstance(n_lp, bool):
+                n_lp = 0 if n_lp else None
+            if n_lp is not None:
+                set_logprobs(sp, True, n_lp)
+        except ValueError as e:
+            return JSONResponse({"error": {"message": str(e).replace("top_logprobs", "logprobs"),
+                                           "type": "invalid_request_error"}}, status_code=400)
         seq = await h.async_engine.generate(ids, sp)
+        choice = {"index": 0, "text": h.tokenizer.decode(seq.output_ids), "finish_reason": seq.finish_reason}
+        if sp.logprobs:
+            ent = lp_entries(h, seq)
+            offs, raw = [], b""
+            for e in ent:
+                offs.append(len(raw.decode("utf-8", errors="replace")))
+                raw += bytes(e["bytes"])
+            choice["logprobs"] = {"tokens": [e["token"] for e in ent], "token_logprobs": [e["logprob"] for e in ent],
+                                  "top_logprobs": [{t["token"]: t["logprob"] for t in e["top_logprobs"]} for e in ent],
+                                  "text_offset": offs}
         return {"id": "cmpl-" + uuid.uuid4().hex[:12], "object": "text_completion", "created": int(time.time()),
-                "model": model, "choices": [{"index": 0, "text": h.tokenizer.decode(seq.output_ids),
-                                             "finish_reason": seq.finish_reason}]}
+                "model": model, "choices": [choice]}
 
     @app.post("/v1/embeddings")
     async def oa_emb(request: Request):

@@ -39,6 +39,8 @@ log = get_logger("serving.remote")
 class _SeqView:
     """What the HTTP app reads off a finished engine sequence."""
     output_ids: list = field(default_factory=list)
+    # (chosen logprob, [(id, logprob), ...]) per output id of a request that asked (else empty)
+    logprobs: list = field(default_factory=list)
     num_cached_prefix: int = 0
     finish_reason: Optional[str] = None
     error: Optional[str] = None
@@ -147,11 +149,14 @@ class CoreClient:
                 item = await q.get()
                 if item is None:
                     raise asyncio.TimeoutError()
-                _, toks, fin, reason, cached, err = item
+                _, toks, fin, reason, cached, err = item[:6]
+                lps = item[6] if len(item) > 6 else None  # only a request that asked has it
                 if toks and view.first_token_at is None:
                     view.first_token_at = time.time()
                 for i, t in enumerate(toks):
                     view.output_ids.append(t)
+                    if lps is not None and i < len(lps) and lps[i] is not None:
+                        view.logprobs.append((lps[i][0], [(int(a), b) for a, b in lps[i][1]]))
                     last = fin and i == len(toks) - 1
                     if last:
                         view.finished, view.finish_reason = True, reason

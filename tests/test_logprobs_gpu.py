@@ -1,0 +1,175 @@
+"""Token log-probability kernel (csrc/sampling.hip lk_token_logprobs) against float64
+``log_softmax`` of the same stored values (bf16 is upcast, not re-rounded) and a stable
+descending sort: ids must match exactly, log-probabilities within an absolute 1e-4.
+
+The bound is derived, not measured: x - max rounds by at most 4e-6 for |x| <= 115; the sum of
+128k exponentials, serial per thread and then by tree, carries a relative error of about 1e-5;
+the hardware exp adds about 1e-6; about 2e-5 in total, so 1e-4 is a fivefold margin."""
+import pytest
+import torch
+
+from llm_kubernetes_minikube_sharp4dev_amd import ops
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+TOL = 1e-4
+
+
+def _reference(logits, ids, rows, n):
+    x = logits.detach().cpu().double()[rows]
+    lp = torch.log_softmax(x, dim=-1)
+    chosen = lp.gather(1, ids.cpu().long()[rows][:, None]).squeeze(1)
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, : min(n, x.shape[1])]
+    return chosen, lp.gather(1, order), order
+
+
+def _close(got, want):
+    got = got.cpu().double()
+    fin = torch.isfinite(want)
+    assert torch.equal(got[~fin], want[~fin])  # -inf stays -inf
+    err = (got[fin] - want[fin]).abs().max().item() if fin.any() else 0.0
+    assert err <= TOL, f"max abs error {err:.3e}"
+
+
+def _check(logits, rows, n, ids=None):
+    B = logits.shape[0]
+    if ids is None:
+        ids = torch.randint(0, logits.shape[1], (B,), dtype=torch.int32)
+    rows_t = torch.tensor(rows, dtype=torch.int32, device=DEV)
+    chosen, top_lp, top_id = ops.token_logprobs(logits, ids.to(DEV), rows_t, n)
+    ne = min(n, logits.shape[1])
+    assert chosen.shape == (len(rows),) and top_lp.shape == (len(rows), ne) and top_id.shape == (len(rows), ne)
+    assert chosen.dtype == torch.float32 and top_lp.dtype == torch.float32 and top_id.dtype == torch.int32
+    want_c, want_lp, want_id = _reference(logits, ids, rows, n)
+    assert torch.equal(top_id.cpu().long(), want_id)
+    _close(chosen, want_c)
+    _close(top_lp, want_lp)
+    return chosen, top_lp, top_id
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_real_vocabulary(hip, dtype):
+    torch.manual_seed(0)
+    logits = (torch.randn(8, 128256) * 3).to(dtype).to(DEV)
+    _check(logits, [0, 3, 7], 20)
+
+
+def test_padded_stride_bf16(hip):
+    torch.manual_seed(1)
+    buf = (torch.randn(8, 128264) * 3).to(torch.bfloat16).to(DEV)
+    logits = buf[:, :128256]
+    assert logits.stride(0) == 128264
+    _check(logits, [0, 3, 7], 20)
+
+
+@pytest.mark.parametrize("V,n,dtype", [(1003, 20, torch.float32), (1003, 20, torch.bfloat16), (100, 20, torch.float32),
+                                       (12, 20, torch.float32), (2056, 7, torch.bfloat16)])
+def test_tails_and_small_rows(hip, V, n, dtype):
+    """V % 8 != 0 (and with it rows that are not 16-byte aligned: the element-by-element scan,
+    in f32 and in bf16), fewer elements than threads, n clamped to V, an aligned small row."""
+    torch.manual_seed(2)
+    logits = (torch.randn(4, V) * 3).to(dtype).to(DEV)
+    _, top_lp, _ = _check(logits, [0, 1, 2, 3], n)
+    assert top_lp.shape[1] == min(n, V)
+
+
+def test_aligned_row_with_scalar_tail(hip):
+    """16-byte loads plus the V % 8 tail: V = 1003 inside a [B, 1008] buffer."""
+    torch.manual_seed(3)
+    for dtype in (torch.float32, torch.bfloat16):
+        buf = (torch.randn(4, 1008) * 3).to(dtype).to(DEV)
+        _check(buf[:, :1003], [3, 0], 20)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_overflow(hip, dtype):
+    """exp(x) itself overflows at x ~ 100: pins the subtraction of the row maximum."""
+    torch.manual_seed(4)
+    logits = (torch.randn(4, 128256) * 3 + 100).to(dtype).to(DEV)
+    chosen, top_lp, _ = _check(logits, [1, 2], 20)
+    assert torch.isfinite(chosen).all() and torch.isfinite(top_lp).all()
+
+
+@pytest.mark.parametrize("n", [1, 5, 20])
+def test_ties_across_the_cut(hip, n):
+    torch.manual_seed(5)
+    V = 4096
+    x = torch.randn(2, V) * 3
+    for r in range(2):
+        order = torch.sort(x[r], descending=True, stable=True).indices
+        x[r, order[max(n - 1, 0): n + 2]] = float(x[r, order[n]])  # sorted positions n-1, n, n+1 made equal
+    _, _, top_id = _check(x.to(DEV), [0, 1], n)  # (the stable sort puts the lowest ids first)
+    for r in range(2):
+        tied = (x[r] == x[r, top_id[r, -1].item()]).nonzero().flatten()
+        assert len(tied) >= 3 and top_id[r, -1].item() == tied[0].item()  # one of the three made the cut
+
+
+def test_tie_at_the_maximum(hip):
+    torch.manual_seed(6)
+    x = torch.randn(2, 5000) * 3
+    x[0, 4321] = x[0, 77] = 50.0
+    x[1, 8] = x[1, 4999] = 50.0
+    _, top_lp, top_id = _check(x.to(DEV), [0, 1], 3)
+    assert top_id[:, :2].tolist() == [[77, 4321], [8, 4999]]
+    assert top_lp[0, 0].item() == top_lp[0, 1].item()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_plateau_forces_exact_fallback(hip, dtype):
+    """6000 elements at the row maximum exceed the candidate list."""
+    torch.manual_seed(7)
+    V = 32768
+    x = torch.randn(2, V) * 3
+    plateau = torch.randperm(V)[:6000].sort().values
+    x[0, plateau] = 40.0
+    x[1, plateau] = 40.0
+    x[1, 31000] = 41.0  # one element above the plateau: it leads, then the first four ties
+    _, _, top_id = _check(x.to(dtype).to(DEV), [0, 1], 5)
+    assert top_id[0].tolist() == plateau[:5].tolist()
+    assert top_id[1].tolist() == [31000] + [int(i) for i in plateau[plateau != 31000][:4]]
+
+
+def test_neg_inf_entries(hip):
+    torch.manual_seed(8)
+    V = 20000
+    x = torch.randn(3, V) * 3
+    x[torch.rand(3, V) < 0.9] = float("-inf")
+    x[2, 16:] = float("-inf")  # 16 or fewer finite entries: the top 20 reach into the -inf ones, by id
+    ids = torch.tensor([int(torch.isfinite(x[0]).nonzero()[0]), int(torch.isinf(x[1]).nonzero()[0]), 5], dtype=torch.int32)
+    chosen, top_lp, _ = _check(x.to(DEV), [0, 1, 2], 20, ids=ids)
+    assert chosen[1].item() == float("-inf")
+    assert torch.isfinite(top_lp[:2]).all() and torch.isinf(top_lp[2, 16:]).all()
+
+
+def test_n_zero_and_no_rows(hip):
+    torch.manual_seed(9)
+    logits = (torch.randn(4, 1024) * 3).to(DEV)
+    ids = torch.randint(0, 1024, (4,), dtype=torch.int32)
+    chosen, top_lp, top_id = _check(logits, [2, 0], 0, ids=ids)
+    assert top_lp.shape == (2, 0) and top_id.shape == (2, 0)
+    chosen, top_lp, top_id = ops.token_logprobs(logits, ids.to(DEV), torch.empty(0, dtype=torch.int32, device=DEV), 20)
+    assert chosen.shape == (0,) and top_lp.shape == (0, 20) and top_id.shape == (0, 20)
+
+
+@pytest.mark.parametrize("n", [21, -1])
+def test_bad_n_raises(hip, n):
+    logits = torch.randn(2, 1024, device=DEV)
+    ids = torch.zeros(2, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError):
+        ops.token_logprobs(logits, ids, torch.tensor([0], dtype=torch.int32, device=DEV), n)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_row_mapping_and_read_only_logits(hip, dtype):
+    """Out-of-order rows with ids = each row's argmax: the chosen token heads its own row's top
+    list, and the logits are bit-identical after the call."""
+    torch.manual_seed(10)
+    logits = (torch.randn(16, 5003) * 3).to(dtype).to(DEV)
+    before = logits.clone()
+    ids = torch.sort(logits.cpu().float(), dim=-1, descending=True, stable=True).indices[:, 0].int()
+    rows = [15, 2, 9]
+    chosen, top_lp, top_id = _check(logits, rows, 4, ids=ids)
+    assert torch.equal(chosen, top_lp[:, 0])
+    assert top_id[:, 0].tolist() == [int(ids[r]) for r in rows]
+    assert torch.equal(logits.view(torch.int16 if dtype == torch.bfloat16 else torch.int32),
+                       before.view(torch.int16 if dtype == torch.bfloat16 else torch.int32))
