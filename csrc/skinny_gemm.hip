@@ -465,6 +465,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
                                                             bf16_t* __restrict__ out, long ldo) {
   const int q = n_out / 4;
   const long total = (long)M * q;
+  // (as the GEMM's own S = 1 stores: 8-B vectors only into 8-B aligned rows)
+  const bool out_vec = ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int row = (int)(i / q), c4 = (int)(i % q) * 4;
     const float* p = part + (long)row * ld + c4;
@@ -480,10 +482,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 4; ++j) y[j] = v[j];
     }
-    uint2 pk;
-    pk.x = pack_bf2(y[0], y[1]);
-    pk.y = pack_bf2(y[2], y[3]);
-    *reinterpret_cast<uint2*>(out + (long)row * ldo + c4) = pk;
+    bf16_t* dst = out + (long)row * ldo + c4;
+    if (out_vec) {
+      uint2 pk;
+      pk.x = pack_bf2(y[0], y[1]);
+      pk.y = pack_bf2(y[2], y[3]);
+      *reinterpret_cast<uint2*>(dst) = pk;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dst[j] = f2bf(y[j]);
+    }
   }
 }
 
