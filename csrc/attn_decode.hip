@@ -371,8 +371,8 @@ int lk_paged_decode(const bf16_t* q, long qs, const bf16_t* kc, const bf16_t* vc
 #undef BY_G
 #undef LAUNCH
   LK_CHECK_LAUNCH();
-  // (fused: the last split merges; reduce == 0: the consumer merges -- the O projection's
-  // weight-streaming prologue, lk_wsgemm_pro kind 2)
+  // (fused: the last split merges; reduce == 0: the partials are left as written -- the route by
+  // which tests/test_attention_exact_gpu.py pins them)
   if ((max_splits > 1 || pp_o) && tickets == nullptr && reduce) {
     if (D == 128)
       decode_reduce_kernel<128><<<dim3(Hq, B), 128, 0, st>>>(part_o, part_ml, ctx_lens, out, os, Hq,

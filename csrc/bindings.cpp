@@ -270,118 +270,6 @@ at::Tensor ws_linear_rope_kv(const at::Tensor& x, const at::Tensor& w, const at:
   return qkv;
 }
 
-// Weight-streaming GEMM whose workgroups compute their own X rows first (lk_wsgemm_pro):
-//   kind 1: x (written) = RMSNorm(bf16(sum of pp's slabs) + res_in) * gamma; res_out = the summed
-//           residual (a tensor other than res_in)
-//   kind 2: x = the paged-decode output, rows with > 1 split merged from (po, pml) first
-// Returns the f32 partial slabs [S, M, N] when S > 1 (reduce == false), else the bf16 (SwiGLU)
-// output.
-at::Tensor ws_pro(at::Tensor& x, const at::Tensor& w, bool swiglu, int64_t bn, int64_t splits, int64_t kind,
-                  bool reduce, const c10::optional<at::Tensor>& pp, const c10::optional<at::Tensor>& res_in,
-                  const c10::optional<at::Tensor>& res_out, const c10::optional<at::Tensor>& gamma, double eps,
-                  const c10::optional<at::Tensor>& po, const c10::optional<at::Tensor>& pml,
-                  const c10::optional<at::Tensor>& ctx, int64_t split, int64_t max_splits, int64_t Hq) {
-  CHECK_CUDA(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "ws_pro: x [M,K], w [N,K]");
-  check_rows16(x, "x"); check_rows16(w, "w");
-  const int M = x.size(0), K = x.size(1), N = w.size(0), S = (int)splits;
-  TORCH_CHECK(M >= 1 && M <= 64 && S >= 1, "ws_pro: 1 <= M <= 64, splits >= 1");
-  const int n_out = swiglu ? N / 2 : N;
-  at::Tensor part, out;
-  if (S > 1) part = at::empty({(long)S, M, N}, x.options().dtype(at::kFloat));
-  if (kind == 0) {  // plain X: the partial slabs only (the producer of a kind-1 consumer)
-    TORCH_CHECK(S > 1 && !swiglu, "ws_pro kind 0: split-K partials (splits > 1, no SwiGLU)");
-    CHECK_RC(lk_wsgemm_part(bp(x), x.stride(0), bp(w), M, N, K, (int)bn, S, part.data_ptr<float>(), cur_stream()),
-             "ws_pro (part)");
-    return part;
-  }
-  if (S == 1 || reduce) out = at::empty({M, n_out}, x.options());
-  const float* ppp = nullptr;
-  int pS = 0;
-  const bf16_t* rin = nullptr;
-  bf16_t* rout = nullptr;
-  long rs = 0;
-  const bf16_t* g = nullptr;
-  if (kind == 1) {
-    TORCH_CHECK(pp && res_in && res_out && gamma, "ws_pro kind 1: pp, res_in, res_out, gamma");
-    CHECK_CUDA(*pp); CHECK_F32(*pp); CHECK_CONTIG(*pp);
-    TORCH_CHECK(pp->dim() == 3 && pp->size(1) == M && pp->size(2) == K, "pp must be [S, M, K]");
-    CHECK_BF16(*res_in); CHECK_BF16(*res_out); CHECK_CONTIG(*res_in); CHECK_CONTIG(*res_out);
-    TORCH_CHECK(res_in->size(0) == M && res_in->size(1) == K && res_out->sizes() == res_in->sizes(), "residual shapes");
-    TORCH_CHECK(res_in->data_ptr() != res_out->data_ptr(), "res_out must not alias res_in");
-    CHECK_BF16(*gamma); TORCH_CHECK(gamma->numel() == K && gamma->is_contiguous(), "gamma [K]");
-    ppp = pp->data_ptr<float>();
-    pS = pp->size(0);
-    rin = bp(*res_in);
-    rout = bp(*res_out);
-    rs = res_in->stride(0);
-    g = bp(*gamma);
-  }
-  const float* pop = nullptr;
-  const float* pmp = nullptr;
-  const int* cp = nullptr;
-  int D = 0;
-  if (kind == 2) {
-    TORCH_CHECK(po && pml && ctx, "ws_pro kind 2: po, pml, ctx");
-    CHECK_F32(*po); CHECK_F32(*pml); CHECK_CONTIG(*po); CHECK_CONTIG(*pml); CHECK_I32(*ctx); CHECK_CONTIG(*ctx);
-    TORCH_CHECK(Hq > 0 && K % Hq == 0, "Hq");
-    D = K / Hq;
-    TORCH_CHECK(po->numel() >= (long)M * Hq * max_splits * D && pml->numel() >= (long)M * Hq * max_splits * 2 &&
-                ctx->numel() >= M, "decode partials / ctx too small");
-    pop = po->data_ptr<float>();
-    pmp = pml->data_ptr<float>();
-    cp = ctx->data_ptr<int>();
-  }
-  int rc = lk_wsgemm_pro((int)kind, bp(x), bp(w), M, N, K, (int)bn, S, swiglu ? 1 : 0,
-                         out.defined() ? bp(out) : nullptr, out.defined() ? out.stride(0) : 0,
-                         S > 1 ? part.data_ptr<float>() : nullptr, ppp, pS, rin, rout, rs, g, (float)eps, pop, pmp, cp,
-                         (int)Hq, D, (int)max_splits, (int)split, cur_stream());
-  CHECK_RC(rc, "ws_pro");
-  return out.defined() ? out : part;
-}
-
-// rope_kv_ over the reduce of split-K QKV slabs part [S, M, N] (as ws_linear_rope_kv's second half)
-at::Tensor splitk_rope_kv(const at::Tensor& part, const at::Tensor& positions, const at::Tensor& cos_sin, int64_t Hq,
-                          int64_t Hkv, int64_t D, const c10::optional<at::Tensor>& k_cache,
-                          const c10::optional<at::Tensor>& v_cache, const c10::optional<at::Tensor>& slots, bool neox,
-                          bool write_k_inplace) {
-  CHECK_CUDA(part); CHECK_F32(part); CHECK_CONTIG(part);
-  TORCH_CHECK(part.dim() == 3 && part.size(2) == (Hq + 2 * Hkv) * D, "part must be [S, M, (Hq + 2 Hkv) * D]");
-  const int S = part.size(0), M = part.size(1), N = part.size(2);
-  CHECK_I32(positions); CHECK_F32(cos_sin); CHECK_CONTIG(cos_sin); CHECK_CONTIG(positions);
-  TORCH_CHECK(positions.numel() == M, "positions");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
-  int BS = 1;
-  if (k_cache || v_cache) {
-    TORCH_CHECK(k_cache && v_cache && slots, "k_cache, v_cache and slots go together");
-    CHECK_BF16(*k_cache); CHECK_BF16(*v_cache); CHECK_CONTIG(*k_cache); CHECK_CONTIG(*v_cache);
-    CHECK_I32(*slots); TORCH_CHECK(slots->numel() == M, "slots");
-    TORCH_CHECK(k_cache->dim() == 4 && k_cache->size(1) == Hkv && k_cache->size(3) == D, "k_cache must be [NB, Hkv, BS, D]");
-    TORCH_CHECK(v_cache->sizes() == k_cache->sizes(), "v_cache shape");
-    BS = k_cache->size(2);
-  }
-  at::Tensor qkv = at::empty({M, N}, part.options().dtype(at::kBFloat16));
-  int rc = lk_splitk_rope_kv(part.data_ptr<float>(), S, bp(qkv), qkv.stride(0), ip(positions), cos_sin.data_ptr<float>(),
-                             M, (int)Hq, (int)Hkv, (int)D, bpo(k_cache), bpo(v_cache), ipo(slots), BS, neox ? 1 : 0,
-                             write_k_inplace ? 1 : 0, cur_stream());
-  CHECK_RC(rc, "splitk_rope_kv");
-  return qkv;
-}
-
-// RMSNorm(bf16(sum of part's slabs) + residual) * w, residual updated in place (lk_splitk_rmsnorm)
-at::Tensor splitk_rmsnorm(const at::Tensor& part, at::Tensor& residual, const at::Tensor& w, double eps) {
-  CHECK_CUDA(part); CHECK_F32(part); CHECK_CONTIG(part);
-  CHECK_BF16(residual); CHECK_LASTDIM(residual); CHECK_BF16(w); check_rows16(residual, "residual");
-  TORCH_CHECK(part.dim() == 3 && part.size(1) == residual.size(0) && part.size(2) == residual.size(1), "part [S, M, H]");
-  const long M = residual.size(0);
-  const int H = residual.size(1);
-  TORCH_CHECK(w.numel() == H && w.is_contiguous(), "w [H]");
-  at::Tensor out = at::empty({M, H}, residual.options());
-  CHECK_RC(lk_splitk_rmsnorm(bp(out), bp(residual), part.data_ptr<float>(), part.size(0), bp(w), M, H, (float)eps,
-                             out.stride(0), residual.stride(0), cur_stream()), "splitk_rmsnorm");
-  return out;
-}
-
 // Decode GEMV for M <= 2 rows (csrc/gemv_decode.hip).  mode 0: returns x.w^T; 1: res += x.w^T in
 // place (returns res); 2: SwiGLU over w = [Wg; Wu] (returns [M, N/2]); 3: RoPE + paged-KV write of a
 // packed QKV projection (returns the qkv rows).  gamma: RMSNorm(x) * gamma is the GEMV's input.
@@ -389,20 +277,9 @@ at::Tensor gemv_decode(int64_t mode, const at::Tensor& x, const at::Tensor& w, c
                        double eps, const c10::optional<at::Tensor>& res, const c10::optional<at::Tensor>& positions,
                        const c10::optional<at::Tensor>& cos_sin, int64_t Hq, int64_t Hkv, int64_t D,
                        const c10::optional<at::Tensor>& k_cache, const c10::optional<at::Tensor>& v_cache,
-                       const c10::optional<at::Tensor>& slots, bool neox, const c10::optional<at::Tensor>& po,
-                       const c10::optional<at::Tensor>& pml, const c10::optional<at::Tensor>& ctx,
-                       int64_t max_splits, int64_t split) {
+                       const c10::optional<at::Tensor>& slots, bool neox) {
   CHECK_CUDA(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_LASTDIM(x); CHECK_CONTIG(w);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "gemv_decode: x [M,K], w [N,K]");
-  if (po) {  // the O projection merging the paged-decode split partials of x's rows
-    TORCH_CHECK(mode == 1 && pml && ctx && !gamma, "gemv_decode merge prologue: mode 1 with pml, ctx, no gamma");
-    CHECK_F32(*po); CHECK_F32(*pml); CHECK_I32(*ctx); CHECK_CONTIG(*po); CHECK_CONTIG(*pml);
-    TORCH_CHECK(po->dim() == 4 && po->size(0) >= x.size(0) && po->size(1) == Hq && po->size(2) == max_splits &&
-                    po->size(3) == D && Hq * D == x.size(1), "po [M, Hq, max_splits, D]");
-    TORCH_CHECK(pml->dim() == 4 && pml->size(0) == po->size(0) && pml->size(1) == Hq && pml->size(2) == max_splits &&
-                    pml->size(3) == 2, "pml [M, Hq, max_splits, 2]");
-    TORCH_CHECK(ctx->numel() >= x.size(0) && split > 0, "ctx: one per row; split > 0");
-  }
   check_rows16(x, "x"); check_rows16(w, "w");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(lk_gemv_supported(M, N, K, (int)mode), "gemv_decode: unsupported shape M", M, " N", N, " K", K);
@@ -445,9 +322,7 @@ at::Tensor gemv_decode(int64_t mode, const at::Tensor& x, const at::Tensor& w, c
   }
   CHECK_RC(lk_gemv_decode((int)mode, bp(x), x.stride(0), bpo(gamma), (float)eps, bp(w), M, N, K,
                           mode == 1 ? nullptr : bp(out), mode == 1 ? 0 : out.stride(0), rp, ldr, pos, cs, (int)Hq,
-                          (int)Hkv, (int)D, kc, vc, sl, BS, neox ? 1 : 0, po ? po->data_ptr<float>() : nullptr,
-                          pml ? pml->data_ptr<float>() : nullptr, ctx ? ip(*ctx) : nullptr, (int)max_splits,
-                          (int)split, cur_stream()),
+                          (int)Hkv, (int)D, kc, vc, sl, BS, neox ? 1 : 0, cur_stream()),
            "gemv_decode");
   return out;
 }
@@ -1171,34 +1046,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_split_size", &decode_split_size);
   m.def("paged_decode", &paged_decode, "", py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"), py::arg("ctx_lens"), py::arg("max_splits"), py::arg("split"), py::arg("scale"), py::arg("part_o") = py::none(), py::arg("part_ml") = py::none(), py::arg("out") = py::none(), py::arg("k_start") = py::none(), py::arg("pp_o") = py::none(), py::arg("pp_ml") = py::none(), py::arg("tickets") = py::none(), py::arg("reduce") = true);
   m.def("prefill_rows_per_tile", &prefill_rows_per_tile);
-  m.def("ws_pro", &ws_pro, "", py::arg("x"), py::arg("w"), py::arg("swiglu"), py::arg("bn"), py::arg("splits"),
-        py::arg("kind"), py::arg("reduce") = false, py::arg("pp") = py::none(), py::arg("res_in") = py::none(),
-        py::arg("res_out") = py::none(), py::arg("gamma") = py::none(), py::arg("eps") = 0.0,
-        py::arg("po") = py::none(), py::arg("pml") = py::none(), py::arg("ctx") = py::none(), py::arg("split") = 0,
-        py::arg("max_splits") = 0, py::arg("Hq") = 0);
-  m.def("splitk_rope_kv", &splitk_rope_kv);
-  m.def("splitk_rmsnorm", &splitk_rmsnorm);
   m.def("gemv_decode", &gemv_decode, "", py::arg("mode"), py::arg("x"), py::arg("w"), py::arg("gamma") = py::none(),
         py::arg("eps") = 1e-5, py::arg("res") = py::none(), py::arg("positions") = py::none(),
         py::arg("cos_sin") = py::none(), py::arg("Hq") = 0, py::arg("Hkv") = 0, py::arg("D") = 0,
         py::arg("k_cache") = py::none(), py::arg("v_cache") = py::none(), py::arg("slots") = py::none(),
-        py::arg("neox") = true, py::arg("po") = py::none(), py::arg("pml") = py::none(), py::arg("ctx") = py::none(),
-        py::arg("max_splits") = 0, py::arg("split") = 0);
+        py::arg("neox") = true);
   m.def("gemv_supported", [](int64_t M, int64_t N, int64_t K, int64_t mode) {
     return lk_gemv_supported((int)M, (int)N, (int)K, (int)mode) != 0;
   });
   m.def("gemv_set_wgs", [](int64_t n) { lk_gemv_set_wgs((int)n); });
   m.def("gemv_set_ksplit", [](bool on) { lk_gemv_set_ksplit(on ? 1 : 0); });
-  // read rows [r0, r1) of a contiguous 2-D tensor through the Infinity Cache (lk_l3_prefetch)
-  m.def("l3_prefetch", [](const at::Tensor& t, int64_t r0, int64_t r1, int64_t wgs, at::Tensor& sink) {
-    CHECK_CUDA(t); CHECK_CONTIG(t); CHECK_CUDA(sink);
-    TORCH_CHECK(sink.scalar_type() == at::kInt && sink.numel() >= 1, "sink: int32 [>= 1]");
-    TORCH_CHECK(t.dim() == 2 && 0 <= r0 && r0 <= r1 && r1 <= t.size(0), "rows out of range");
-    const long row = t.size(1) * t.element_size();
-    const char* base = reinterpret_cast<const char*>(t.data_ptr()) + r0 * row;
-    CHECK_RC(lk_l3_prefetch(base, (r1 - r0) * row, (int)wgs, reinterpret_cast<unsigned*>(sink.data_ptr<int>()),
-                            cur_stream()), "l3_prefetch");
-  });
   m.def("ws_set_variant", [](int64_t M, int64_t N, int64_t K, bool swiglu, int64_t v) {
     CHECK_RC(lk_wsgemm_set_variant((int)M, (int)N, (int)K, swiglu ? 1 : 0, (int)v), "ws_set_variant");
   }, "weight-streaming GEMM kernel for this (M bucket, N, K, swiglu): 0 ring, 1 loader waves, -1 default",

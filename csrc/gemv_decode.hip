@@ -13,8 +13,7 @@
 //     each pair two waves, a K half each, joined in LDS (KW = 2);
 //   * X (the M input rows) is staged once per workgroup in LDS by LDS-DMA; the NORM prologue
 //     computes RMSNorm(res) * gamma there itself (the rmsnorm kernel's exact arithmetic), so the
-//     producer of res never launches a norm; PRO 2 (the O projection, opt-in: measured slower)
-//     merges the paged-decode split partials there instead of a decode_reduce launch;
+//     producer of res never launches a norm;
 //   * epilogues on the pair's two dot products: 0 plain bf16 out, 1 res += out (the residual
 //     stream updated in place, each element owned by one wave), 2 SwiGLU (pair = gate row p,
 //     up row I + p: the splitk_reduce_kernel<true> arithmetic), 3 RoPE + paged-KV write (pair =
@@ -50,11 +49,6 @@ struct GemvArgs {
   bf16_t* kc = nullptr;
   bf16_t* vc = nullptr;
   const int* slots = nullptr;
-  // PRO 2 (O projection): the paged-decode split partials of X's rows, merged in the prologue
-  const float* po = nullptr;   // [(row * Hq + h) * max_splits + s][D]
-  const float* pml = nullptr;  // [(row * Hq + h) * max_splits + s][2] (max in the log2 domain, sum)
-  const int* ctx = nullptr;
-  int max_splits = 0, split = 0;
 };
 
 typedef __attribute__((address_space(3))) void* gemv_lptr;
@@ -73,9 +67,8 @@ LK_DEVICE void dot8(const uint4_t wv, const uint4_t xv, float& acc) {
   }
 }
 
-template <int MR, int PRO, int MODE, int U, int KW>
+template <int MR, bool NORM, int MODE, int U, int KW>
 __global__ __launch_bounds__(256) void gemv_decode_kernel(GemvArgs g) {
-  constexpr bool NORM = PRO == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);  // [MR][K]
   __shared__ float red[4 * MR];
@@ -111,51 +104,13 @@ __global__ __launch_bounds__(256) void gemv_decode_kernel(GemvArgs g) {
   // for the whole prologue -- a load -> store loop serialised K / 2048 of them); chunk c of row m
   // lands at xs + m * K + 8 c (64 consecutive chunks per wave instruction: nch % 64 == 0)
   bf16_t* gs = xs + MR * K;  // NORM: gamma [K]
-  // PRO 2: rows whose attention ran in more than one split are merged below (flash-decoding merge,
-  // decode_reduce_kernel's arithmetic); the attention kernel wrote the others into x itself
-  int nsp[MR];
-#pragma unroll
-  for (int m = 0; m < MR; ++m)
-    nsp[m] = PRO == 2 ? max(0, min((g.ctx[m] + g.split - 1) / g.split, g.max_splits)) : 1;
   for (int c0 = wv * 64; c0 < nch; c0 += 256) {
 #pragma unroll
     for (int m = 0; m < MR; ++m)
-      if (nsp[m] <= 1)
-        __builtin_amdgcn_global_load_lds((gemv_gptr)(g.x + (long)m * g.ldx + (c0 + lane) * 8),
-                                         (gemv_lptr)(xs + m * K + c0 * 8), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gemv_gptr)(g.x + (long)m * g.ldx + (c0 + lane) * 8),
+                                       (gemv_lptr)(xs + m * K + c0 * 8), 16, 0, 0);
     if constexpr (NORM)
       __builtin_amdgcn_global_load_lds((gemv_gptr)(g.gamma + (c0 + lane) * 8), (gemv_lptr)(gs + c0 * 8), 16, 0, 0);
-  }
-  if constexpr (PRO == 2) {
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const int ns = nsp[m];
-      if (ns <= 1) continue;
-      for (int c = threadIdx.x; c < nch; c += 256) {
-        const int e0 = c * 8, h = e0 / g.D, d0 = e0 - h * g.D;
-        const long base = ((long)m * g.Hq + h) * g.max_splits;
-        float Mx = -INFINITY;
-        for (int q = 0; q < ns; ++q) Mx = fmaxf(Mx, g.pml[(base + q) * 2]);
-        if (Mx == -INFINITY) Mx = 0.f;
-        float den = 0.f, num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int q = 0; q < ns; ++q) {
-          const float f = exp2f(g.pml[(base + q) * 2] - Mx);
-          den += f * g.pml[(base + q) * 2 + 1];
-          const floatx4 a = *reinterpret_cast<const floatx4*>(g.po + (base + q) * g.D + d0);
-          const floatx4 b = *reinterpret_cast<const floatx4*>(g.po + (base + q) * g.D + d0 + 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            num[j] += f * a[j];
-            num[j + 4] += f * b[j];
-          }
-        }
-        float y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = den > 0.f ? num[j] / den : 0.f;
-        store8(xs + m * K + e0, y);
-      }
-    }
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (lgkmcnt / expcnt untouched)
   __syncthreads();
@@ -312,36 +267,12 @@ __global__ __launch_bounds__(256) void gemv_decode_kernel(GemvArgs g) {
   }
 }
 
-// Infinity-Cache (L3) prefetch: default-policy 16-B loads over [p, p + bytes) whose values are
-// folded into one word that is stored only if it equals a value no sum of these loads takes in
-// practice (the loads cannot be dropped).  Launched on a side stream while the latency-bound
-// attention kernels leave HBM idle, so the next projection's weights are read from the 256 MiB L3.
-__global__ __launch_bounds__(256) void l3_prefetch_kernel(const uint4_t* __restrict__ p, long n16,
-                                                          unsigned* __restrict__ sink) {
-  unsigned acc = 0;
-  const long stride = (long)gridDim.x * 256;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 7 * stride < n16; i += 8 * stride) {
-    uint4_t v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = p[i + u * stride];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc ^= v[u][0] ^ v[u][3];
-  }
-  for (; i < n16; i += stride) {
-    const uint4_t v = p[i];
-    acc ^= v[0] ^ v[3];
-  }
-  if (acc == 0x9e3779b9u) sink[0] = acc;
-}
-
 constexpr int kGemvMaxLds = 163840 - 1024;  // dynamic LDS opt-in (the static `red` stays below)
 int g_gemv_wgs = 0;  // target workgroup count (0: the default below)
 int g_gemv_ksplit = 1;  // two waves per pair on the long-K projections (ops.GEMV_KSPLIT)
 
-template <int MR, int PRO, int MODE>
+template <int MR, bool NORM, int MODE>
 int launch_u(const GemvArgs& a, int U, hipStream_t st) {
-  constexpr bool NORM = PRO == 1;
   int target = g_gemv_wgs > 0 ? g_gemv_wgs : 512;
   int wgs = (a.npairs + 3) / 4;
   if (wgs > target) wgs = target;
@@ -357,11 +288,11 @@ int launch_u(const GemvArgs& a, int U, hipStream_t st) {
 #define LK_GEMV_U(UU)                                                                  \
   if (U == UU) {                                                                       \
     if (ks2) {                                                                         \
-      LK_SET_MAX_LDS((gemv_decode_kernel<MR, PRO, MODE, UU, 2>), kGemvMaxLds);        \
-      gemv_decode_kernel<MR, PRO, MODE, UU, 2><<<wgs, 256, lds, st>>>(a);             \
+      LK_SET_MAX_LDS((gemv_decode_kernel<MR, NORM, MODE, UU, 2>), kGemvMaxLds);        \
+      gemv_decode_kernel<MR, NORM, MODE, UU, 2><<<wgs, 256, lds, st>>>(a);             \
     } else {                                                                           \
-      LK_SET_MAX_LDS((gemv_decode_kernel<MR, PRO, MODE, UU, 1>), kGemvMaxLds);        \
-      gemv_decode_kernel<MR, PRO, MODE, UU, 1><<<wgs, 256, lds, st>>>(a);             \
+      LK_SET_MAX_LDS((gemv_decode_kernel<MR, NORM, MODE, UU, 1>), kGemvMaxLds);        \
+      gemv_decode_kernel<MR, NORM, MODE, UU, 1><<<wgs, 256, lds, st>>>(a);             \
     }                                                                                  \
   } else
   LK_GEMV_U(8) LK_GEMV_U(7) LK_GEMV_U(4) return -4;
@@ -378,12 +309,12 @@ int pick_u(int K) {
   return 0;
 }
 
-template <int PRO, int MODE>
+template <bool NORM, int MODE>
 int launch_m(const GemvArgs& a, hipStream_t st) {
   const int U = pick_u(a.K);
   if (!U || a.K % 512) return -2;
-  if (a.M == 1) return launch_u<1, PRO, MODE>(a, U, st);
-  if (a.M == 2) return launch_u<2, PRO, MODE>(a, U, st);
+  if (a.M == 1) return launch_u<1, NORM, MODE>(a, U, st);
+  if (a.M == 2) return launch_u<2, NORM, MODE>(a, U, st);
   return -2;
 }
 
@@ -399,18 +330,11 @@ int lk_gemv_supported(int M, int N, int K, int mode) {
 
 void lk_gemv_set_wgs(int wgs) { g_gemv_wgs = wgs; }
 
-int lk_l3_prefetch(const void* p, long bytes, int wgs, unsigned* sink, hipStream_t st) {
-  if (!p || bytes < 16 || ((uintptr_t)p & 15) || !sink || wgs < 1) return bytes < 16 ? 0 : -1;
-  l3_prefetch_kernel<<<wgs, 256, 0, st>>>(reinterpret_cast<const uint4_t*>(p), bytes / 16, sink);
-  LK_CHECK_LAUNCH();
-  return 0;
-}
 void lk_gemv_set_ksplit(int on) { g_gemv_ksplit = on ? 1 : 0; }
 
 int lk_gemv_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, float eps, const bf16_t* w, int M, int N,
                    int K, bf16_t* out, long ldo, bf16_t* res, long ldr, const int* positions, const float* cos_sin,
-                   int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc, const int* slots, int BS, int neox,
-                   const float* po, const float* pml, const int* ctx, int max_splits, int split, hipStream_t st) {
+                   int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc, const int* slots, int BS, int neox, hipStream_t st) {
   if (!lk_gemv_supported(M, N, K, mode) || !x || !w || ldx % 8) return -1;
   GemvArgs a;
   a.x = x;
@@ -458,21 +382,8 @@ int lk_gemv_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, flo
       return -1;
   }
   const bool norm = gamma != nullptr;
-  if (po) {  // the split merge prologue: the O projection (mode 1) only, no norm
-    if (mode != 1 || norm || !pml || !ctx || Hq <= 0 || D <= 0 || D % 8 || Hq * D != K || max_splits < 1 ||
-        split < 1)
-      return -1;
-    a.po = po;
-    a.pml = pml;
-    a.ctx = ctx;
-    a.Hq = Hq;
-    a.D = D;
-    a.max_splits = max_splits;
-    a.split = split;
-    return launch_m<2, 1>(a, st);
-  }
 #define LK_GEMV_MODE(MD)                                             \
-  if (mode == MD) return norm ? launch_m<1, MD>(a, st) : launch_m<0, MD>(a, st);
+  if (mode == MD) return norm ? launch_m<true, MD>(a, st) : launch_m<false, MD>(a, st);
   LK_GEMV_MODE(0) LK_GEMV_MODE(1) LK_GEMV_MODE(2) LK_GEMV_MODE(3)
 #undef LK_GEMV_MODE
   return -1;

@@ -139,8 +139,7 @@ def decode_tickets(device, n: int):
 
 
 def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale: float, max_splits: Optional[int] = None,
-                 part_o=None, part_ml=None, out=None, split: Optional[int] = None, k_start=None, prefix=None,
-                 reduce: bool = True):
+                 part_o=None, part_ml=None, out=None, split: Optional[int] = None, k_start=None, prefix=None):
     """q [B, Hq, D] -> [B, Hq, D].  ``split`` keys per workgroup (default from
     :func:`decode_split_size`), ``max_splits`` = splits covering the block-table width —
     both static, so the launch is hipGraph-capturable.
@@ -148,9 +147,7 @@ def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale: float, max_
     Cascade: ``k_start`` (device int32 [1]) keys are a prefix shared by every row whose
     attention was computed once for the batch by :func:`flash_prefill` in partial mode
     into ``prefix`` = (o [B, Hq, D], ml [B, Hq, 2]); this call attends the rest and
-    merges (the CPU reference attends everything directly).  ``reduce=False`` (GPU, no
-    tickets): rows with more than one split keep their partials in ``part_o`` / ``part_ml`` for
-    the consumer to merge (:func:`ws_pro` kind 2)."""
+    merges (the CPU reference attends everything directly)."""
     if use_hip(q):
         BS = k_cache.shape[2]
         if split is None:
@@ -159,10 +156,10 @@ def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale: float, max_
             max_splits = decode_splits(block_tables.shape[1] * BS, split)
         pp_o, pp_ml = prefix if prefix is not None else (None, None)
         bh = q.shape[0] * k_cache.shape[1]
-        fused = reduce and (DECODE_FUSED_REDUCE == 2 or (DECODE_FUSED_REDUCE == 1 and bh >= 512))
+        fused = DECODE_FUSED_REDUCE == 2 or (DECODE_FUSED_REDUCE == 1 and bh >= 512)
         tickets = decode_tickets(q.device, bh) if fused else None
         return lib().paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, max_splits, split, scale,
-                                  part_o, part_ml, out, k_start, pp_o, pp_ml, tickets, reduce)
+                                  part_o, part_ml, out, k_start, pp_o, pp_ml, tickets)
     y = ref.paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale)
     if out is not None:
         out.copy_(y)
@@ -855,45 +852,12 @@ def ws_tickets(device):
     return t
 
 
-# Consumer-side prologues in the decode step (csrc/skinny_gemm.hip WsPro, rows <= XPRO_MAX_M, one
-# GPU without TP): the O projection merges the paged-decode split partials itself (no
-# decode_reduce launch) and gate_up / the next layer's QKV compute residual add + RMSNorm of the
-# previous projection's split-K slabs themselves (no rmsnorm launch) -- three launches fewer per
-# layer, bit-identical values (models/llama.py _forward_decode_xpro).  Measured slower at batch 1
-# (decode step 4.23 vs 3.58 ms: every workgroup re-reads and re-normalises the producer's fp32 slabs,
-# and the O projection's merge prologue costs 17 us; profiles/r6_xpro/): off unless LK_DECODE_XPRO=1.
-XPRO = os.environ.get("LK_DECODE_XPRO", "0") == "1"
-XPRO_MAX_M = int(os.environ.get("LK_DECODE_XPRO_MAX_M", "16"))
-_PLAN_CACHE: dict = {}
-
-
-def ws_plan(M: int, N: int, K: int, swiglu: bool = False) -> tuple:
-    """(BN, S) of the weight-streaming GEMM for this shape (lk_wsgemm_plan)."""
-    key = (M, N, K, swiglu)
-    p = _PLAN_CACHE.get(key)
-    if p is None:
-        p = _PLAN_CACHE[key] = tuple(lib().ws_plan(M, N, K, swiglu))
-    return p
-
-
-def ws_pro(x, w, plan, kind: int, swiglu: bool = False, reduce: bool = False, **kw):
-    """Weight-streaming GEMM with a consumer-side X prologue (``kind`` 1: x = RMSNorm(bf16(sum of
-    ``pp``) + ``res_in``) * ``gamma``, ``res_out`` = the summed residual; 2: x = the paged-decode
-    output with its split partials ``po`` / ``pml`` merged; 0: plain x).  Returns the f32 partial
-    slabs [S, M, N] (S > 1 and not ``reduce``) or the bf16 / SwiGLU output."""
-    return lib().ws_pro(x, w, swiglu, plan[0], plan[1], kind, reduce, **kw)
-
-
 # Decode GEMV for one or two rows (csrc/gemv_decode.hip): no split-K slabs, the RMSNorm in the
 # consumer's prologue, residual add / SwiGLU / RoPE + paged-KV write in the epilogue -- a Llama
 # block's batch-1 decode step is QKV -> paged decode -> O -> gate_up -> down, with no reduce, norm
 # or RoPE launch (models/llama.py _forward_decode_gemv).  LK_DECODE_GEMV=0: the weight-streaming path.
 GEMV = os.environ.get("LK_DECODE_GEMV", "1") != "0"
 GEMV_MAX_M = 2
-# LK_GEMV_MERGE=1: the O projection's GEMV merges the paged-decode split partials itself (no
-# decode_reduce launch).  Measured slightly slower at batch 1 (decode step 3.129 / 3.133 vs 3.104 /
-# 3.110 ms: every workgroup re-reads all split partials), so the reduce kernel stays the default
-GEMV_MERGE = os.environ.get("LK_GEMV_MERGE", "0") == "1"
 _GEMV_OK: dict = {}
 
 
@@ -904,23 +868,6 @@ _GEMV_OK: dict = {}
 # LDS-DMA (3.31 vs 3.10; profiles/r6_gemv/).  Workgroup target (LK_GEMV_WGS, 0: 512)
 GEMV_KSPLIT = os.environ.get("LK_GEMV_KSPLIT", "1") != "0"
 GEMV_WGS = int(os.environ.get("LK_GEMV_WGS", "0") or 0)
-
-
-# Batch-1 decode: while the latency-bound paged-decode kernels leave HBM idle, a side stream reads
-# the O projection's weights (and the first LK_GEMV_L3_PREFETCH_MB of gate_up's gate / up rows)
-# through the 256 MiB Infinity Cache so the GEMVs behind the attention read them from L3.
-# -1: off; 0: O only.
-GEMV_L3_MB = int(os.environ.get("LK_GEMV_L3_PREFETCH_MB", "-1") or -1)
-GEMV_L3_WGS = int(os.environ.get("LK_GEMV_L3_WGS", "128") or 128)
-_L3_SINK: dict = {}
-
-
-def l3_prefetch(t, r0: int, r1: int):
-    """Read rows [r0, r1) of a contiguous 2-D GPU tensor (values unused) on the current stream."""
-    s = _L3_SINK.get(t.device)
-    if s is None:
-        s = _L3_SINK[t.device] = torch.zeros(1, dtype=torch.int32, device=t.device)
-    lib().l3_prefetch(t, r0, r1, GEMV_L3_WGS, s)
 
 
 def gemv_supported(M: int, N: int, K: int, mode: int) -> bool:
@@ -944,18 +891,13 @@ def _gemv_ok(x, w, mode: int) -> bool:
 
 
 def gemv_decode(mode: int, x, w, gamma=None, eps: float = 1e-5, res=None, positions=None, cos_sin=None,
-                Hq: int = 0, Hkv: int = 0, D: int = 0, k_cache=None, v_cache=None, slots=None, neox: bool = True,
-                po=None, pml=None, ctx=None, max_splits: int = 0, split: int = 0):
+                Hq: int = 0, Hkv: int = 0, D: int = 0, k_cache=None, v_cache=None, slots=None, neox: bool = True):
     """mode 0: x W^T; 1: ``res`` += x W^T in place (returned); 2: SwiGLU(x [Wg; Wu]^T) [M, N/2];
     3: packed QKV with RoPE applied to q (and to k in the paged cache, k kept unrotated in the
-    row), K/V written at ``slots``.  ``gamma``: the GEMV's input is RMSNorm(x) * gamma.  ``po`` /
-    ``pml`` (mode 1, GPU): x's rows that :func:`paged_decode` (``reduce=False``) left as split
-    partials are merged in the GEMV's prologue (no decode_reduce launch)."""
+    row), K/V written at ``slots``.  ``gamma``: the GEMV's input is RMSNorm(x) * gamma."""
     if use_hip(x):
         return lib().gemv_decode(mode, x, w, gamma, eps, res, positions, cos_sin, Hq, Hkv, D, k_cache, v_cache,
-                                 slots, neox, po, pml, ctx, max_splits, split)
-    if po is not None:
-        raise NotImplementedError("gemv_decode: the split-merge prologue is a GPU kernel")
+                                 slots, neox)
     xin = ref.rmsnorm(x, gamma, eps) if gamma is not None else x
     y = xin.float() @ w.float().t()
     if mode == 0:
@@ -970,16 +912,6 @@ def gemv_decode(mode: int, x, w, gamma=None, eps: float = 1e-5, res=None, positi
     qkv = y.to(x.dtype)
     rope_kv_(qkv, positions, cos_sin, Hq, Hkv, D, k_cache, v_cache, slots, neox, False)
     return qkv
-
-
-def splitk_rope_kv(part, positions, cos_sin, Hq: int, Hkv: int, D: int, k_cache, v_cache, slots, neox: bool,
-                   write_k_inplace: bool = False):
-    return lib().splitk_rope_kv(part, positions, cos_sin, Hq, Hkv, D, k_cache, v_cache, slots, neox, write_k_inplace)
-
-
-def splitk_rmsnorm(part, residual, w, eps: float):
-    """RMSNorm(bf16(sum of part's slabs) + residual) * w; residual updated in place."""
-    return lib().splitk_rmsnorm(part, residual, w, eps)
 
 
 def linear_add_rmsnorm(x, w, residual, norm_w, eps: float):
