@@ -196,8 +196,11 @@ int lk_repeat_penalty(void* logits, int is_bf16, long ls, int B, const int* wind
 // temperature; greedy rows = argmax).  prm: int32 [B, 8] = temperature, top_p, penalty (f32
 // bits), top_k, last_n, slot, reset, seed.  hist: int32 [slots, W] ring, hist_len: [slots].
 // logits (f32, modified in place by the penalty) -> out int32 [B]; the token is appended to the ring.
-int lk_sample(float* logits, long ls, int B, int V, const int* prm, int* hist, int* hist_len, int W,
-              unsigned long long seed, int* out, hipStream_t st);
+// pw: the row width of prm, 8 or 12; 12 adds [8] min_p, [9] presence, [10] frequency penalty
+// (f32 bits), [11] = 0.  bias: null (no row has one) or int32 [B+1 offsets | n ids | n f32 values
+// as bits] with n = bias_n = offsets[B], ids unique within a row; ids outside [0, V) are ignored.
+int lk_sample(float* logits, long ls, int B, int V, const int* prm, int pw, const int* bias, int bias_n, int* hist,
+              int* hist_len, int W, unsigned long long seed, int* out, hipStream_t st);
 // Token log-probabilities: for each requesting batch row rows[r] (R of them, each in [0, B)),
 // log softmax of its logits (bf16 or f32, row stride ls >= V, read only) at ids[rows[r]] ->
 // chosen_lp f32 [R], and at the n' = min(n, V) most likely ids ordered by (value desc, id asc)

@@ -226,6 +226,12 @@ int lk_repeat_penalty(void* logits, int is_bf16, long ls, int B, const int* wind
 //   Greedy rows (T <= 0) take K = 1: the argmax with the lowest index among ties.
 // Row parameters (8 x 32-bit): temperature, top_p, repeat_penalty (f32), top_k, last_n,
 // slot, reset (1 = new sequence: its ring restarts empty), seed (i32).
+// Sampler controls (docs/sampling.md): rows of 12 add [8] min_p, [9] presence, [10] frequency
+// penalty (f32), [11] = 0, and an optional CSR operand carries per-row logit biases.  The chain
+// is bias -> penalties (l = rp(l) - (c * frequency + presence) per unique window token with c
+// occurrences) -> top-k -> temperature softmax -> top-p -> min-p -> draw; greedy rows take
+// the argmax after bias and penalties.  8-wide rows without a bias run the code they always did.
+// With top_k = 0 the candidate list is the kSampKMax largest.
 constexpr int kSampThreads = 1024, kSampKMax = 1024, kCand = 4096;
 
 LK_DEVICE unsigned fkey(float f) {  // order-preserving float -> uint
@@ -238,16 +244,46 @@ LK_DEVICE float keyf(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k
 // One workgroup per row.  The window's tokens are de-duplicated through a V-bit "seen" bitmap
 // in LDS (one atomicOr per entry; the thread that sets a token's bit penalises it): O(window)
 // for any repeat_last_n, including -1 (= the whole ring, sized to max_model_len by the engine).
+// EXT (12-wide rows and / or a bias operand): the row's logit bias first (one thread per CSR
+// entry, ids unique within a row; complete behind a workgroup barrier before a penalty reads a
+// logit), then l = rp(l) - presence by each token's owner, then -- behind a second barrier --
+// one fp32 atomic add of -frequency per window entry: c adds of the same value onto the
+// owner's result, so the sum does not depend on the order the entries arrive in (the same
+// bits run to run), in O(window) and with no memory but the row itself.
+template <bool EXT>
 __global__ __launch_bounds__(256) void sample_penalty_kernel(float* __restrict__ logits, long ls, int V,
-                                                             const int* __restrict__ prm,
+                                                             const int* __restrict__ prm, int pw,
+                                                             const int* __restrict__ bias, int bias_n,
                                                              const int* __restrict__ hist,
                                                              const int* __restrict__ hist_len, int W) {
   extern __shared__ unsigned seen[];
   const int row = blockIdx.x;
-  const int* p = prm + row * 8;
+  const int* p = EXT ? prm + (long)row * pw : prm + row * 8;
   const float pen = __int_as_float(p[2]);
   const int last_n = p[4], slot = p[5], reset = p[6];
-  if (pen == 1.f || last_n == 0) return;  // uniform per workgroup
+  float presence = 0.f, freq = 0.f;
+  float* lp = logits + (long)row * ls;
+  if constexpr (EXT) {
+    if (pw == 12) {
+      presence = __int_as_float(p[9]);
+      freq = __int_as_float(p[10]);
+    }
+    if (bias) {  // uniform per workgroup
+      const int B = gridDim.x;
+      // offsets clamped to the buffer's own n entries: a malformed operand reads nothing outside it
+      const int b0 = min(max(bias[row], 0), bias_n), b1 = min(bias[row + 1], bias_n);
+      const int* ids = bias + B + 1;
+      const int* val = ids + bias_n;
+      for (int j = b0 + threadIdx.x; j < b1; j += blockDim.x) {
+        const int id = ids[j];
+        if (id >= 0 && id < V) lp[id] += __int_as_float(val[j]);  // -inf (a grammar mask) stays -inf
+      }
+    }
+    __syncthreads();  // every thread of the workgroup: the bias is complete before a penalty reads
+    if ((pen == 1.f && presence == 0.f && freq == 0.f) || last_n == 0) return;  // uniform per workgroup
+  } else {
+    if (pen == 1.f || last_n == 0) return;  // uniform per workgroup
+  }
   const int hl = reset ? 0 : hist_len[slot];
   const int n = min(min(hl, last_n > 0 ? last_n : W), W);
   if (n == 0) return;
@@ -255,14 +291,26 @@ __global__ __launch_bounds__(256) void sample_penalty_kernel(float* __restrict__
   for (int i = threadIdx.x; i < words; i += blockDim.x) seen[i] = 0u;
   __syncthreads();
   const int* h = hist + (long)slot * W;
-  float* lp = logits + (long)row * ls;
   for (int j = threadIdx.x; j < n; j += blockDim.x) {
     const int tok = h[(hl - 1 - j) % W];
     if (tok < 0 || tok >= V) continue;
     const unsigned bit = 1u << (tok & 31);
     if (atomicOr(&seen[tok >> 5], bit) & bit) continue;  // another entry of the window owns it
     const float l = lp[tok];
-    lp[tok] = l > 0.f ? l / pen : l * pen;
+    float x = l > 0.f ? l / pen : l * pen;
+    if constexpr (EXT) {
+      if (presence != 0.f) x -= presence;
+    }
+    lp[tok] = x;
+  }
+  if constexpr (EXT) {
+    if (freq == 0.f) return;  // uniform per workgroup
+    __syncthreads();          // every owner's store is done before the counts land on it
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+      const int tok = h[(hl - 1 - j) % W];
+      if (tok < 0 || tok >= V) continue;
+      atomicAdd(&lp[tok], -freq);
+    }
   }
 }
 
@@ -307,6 +355,8 @@ LK_DEVICE void bitonic(unsigned* key, int* idx, int n) {
   }
 }
 
+// WIDE: 12-wide parameter rows; [8] = min_p joins the top-p cut in step 4
+template <bool WIDE>
 __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float* __restrict__ logits, long ls, int V,
                                                                    const int* __restrict__ prm,
                                                                    int* __restrict__ hist,
@@ -317,8 +367,11 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
   __shared__ float wsum[16];
   __shared__ int ncand_s, thr_s, above_s;
   const int row = blockIdx.x, tid = threadIdx.x;
-  const int* p = prm + row * 8;
+  // (8-wide: the 32-bit offset this kernel always used.  A 64-bit one is an instruction shorter, moves
+  // the sort loops 4 bytes and measured 0.5 % slower: docs/sampling.md)
+  const int* p = WIDE ? prm + (long)row * 12 : prm + row * 8;
   const float temp = __int_as_float(p[0]), top_p = __int_as_float(p[1]);
+  const float min_p = WIDE ? __int_as_float(p[8]) : 0.f;
   const int top_k = p[3], slot = p[5], reset = p[6], rseed = p[7];
   const bool greedy = temp <= 0.f;
   const int K = greedy ? 1 : min(top_k > 0 ? top_k : kSampKMax, min(V, kSampKMax));
@@ -437,7 +490,10 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
     if (tid == k_eff - 1) tot_s = incl;
     if (tid == 0) nkeep_s = 0;
     __syncthreads();
-    const bool keep = tid < k_eff && (incl - e) <= top_p * tot_s;
+    // min-p: p_i >= min_p * p_0, i.e. e_i >= min_p (e_0 = 1); e falls with i, so this is a prefix
+    // too and the kept set is the shorter of the two (candidate 0 always stays)
+    bool keep = tid < k_eff && (incl - e) <= top_p * tot_s;
+    if constexpr (WIDE) keep = keep && (min_p <= 0.f || tid == 0 || e >= min_p);
     if (keep) atomicMax(&nkeep_s, tid + 1);
     __syncthreads();
     if (tid == nkeep_s - 1) keep_s = incl;
@@ -464,17 +520,27 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
   }
 }
 
-int lk_sample(float* logits, long ls, int B, int V, const int* prm, int* hist, int* hist_len, int W,
-              unsigned long long seed, int* out, hipStream_t st) {
+int lk_sample(float* logits, long ls, int B, int V, const int* prm, int pw, const int* bias, int bias_n, int* hist,
+              int* hist_len, int W, unsigned long long seed, int* out, hipStream_t st) {
   if (B <= 0) return 0;
-  if (V < 1 || W < 1) return -1;
+  if (V < 1 || W < 1 || (pw != 8 && pw != 12) || (bias && bias_n < 0)) return -1;
   const size_t seen_bytes = (size_t)((V + 31) >> 5) * 4;
   if (seen_bytes > 160 * 1024) return -1;  // the LDS "seen" bitmap: V <= 1.3M
-  if (seen_bytes > 64 * 1024) {
-    LK_SET_MAX_LDS(sample_penalty_kernel, 160 * 1024);
+  if (pw == 12 || bias) {
+    if (seen_bytes > 64 * 1024) {
+      LK_SET_MAX_LDS(sample_penalty_kernel<true>, 160 * 1024);
+    }
+    sample_penalty_kernel<true><<<B, 256, seen_bytes, st>>>(logits, ls, V, prm, pw, bias, bias_n, hist, hist_len, W);
+  } else {
+    if (seen_bytes > 64 * 1024) {
+      LK_SET_MAX_LDS(sample_penalty_kernel<false>, 160 * 1024);
+    }
+    sample_penalty_kernel<false><<<B, 256, seen_bytes, st>>>(logits, ls, V, prm, 8, nullptr, 0, hist, hist_len, W);
   }
-  sample_penalty_kernel<<<B, 256, seen_bytes, st>>>(logits, ls, V, prm, hist, hist_len, W);
-  sample_topkp_kernel<<<B, kSampThreads, 0, st>>>(logits, ls, V, prm, hist, hist_len, W, seed, out);
+  LK_CHECK_LAUNCH();
+  if (pw == 12) sample_topkp_kernel<true><<<B, kSampThreads, 0, st>>>(logits, ls, V, prm, hist, hist_len, W, seed, out);
+  else sample_topkp_kernel<false><<<B, kSampThreads, 0, st>>>(logits, ls, V, prm, hist, hist_len, W, seed, out);
+  LK_CHECK_LAUNCH();
   return 0;
 }
 

@@ -25,8 +25,10 @@ log = get_logger("engine")
 
 
 def _plain_greedy(p: SamplingParams) -> bool:
-    # (a request for log-probabilities needs the step's logits: the sampler's logits path)
-    return (p.is_greedy and p.logits_processor is None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
+    # (a request for log-probabilities needs the step's logits: the sampler's logits path; so does
+    # a logit bias or a presence / frequency penalty.  Under TP this is also what keeps such a row
+    # out of the vocab-parallel argmax shortcut: StepInfo.greedy is all(_plain_greedy))
+    return (p.is_greedy and p.logits_processor is None and not p.reads_ring and not p.logit_bias
             and not p.logprobs)
 
 
@@ -44,12 +46,11 @@ GEMM_HEALTH_EVERY = int(os.environ.get("LK_GEMM_HEALTH_EVERY", "512"))
 
 
 def _jump_ok(p: SamplingParams) -> bool:
-    """Forced tokens can be appended without sampling: a grammar is set, and no repeat
-    penalty reads the device history ring the sampler kernel appends to (host-appended
-    tokens would be missing from it), and no log-probabilities are asked for (a host-appended
-    token has no logits row of its own to take them from)."""
-    return (p.logits_processor is not None and (p.repeat_penalty == 1.0 or p.repeat_last_n == 0)
-            and not p.logprobs)
+    """Forced tokens can be appended without sampling: a grammar is set, and no repeat,
+    presence or frequency penalty reads the device history ring the sampler kernel appends to
+    (host-appended tokens would be missing from it), and no log-probabilities are asked for (a
+    host-appended token has no logits row of its own to take them from)."""
+    return p.logits_processor is not None and not p.reads_ring and not p.logprobs
 
 
 def _small_buckets() -> tuple:

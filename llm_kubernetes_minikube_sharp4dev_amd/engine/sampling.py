@@ -8,7 +8,9 @@ the last 64 tokens, which is what an OllamaSharp client gets: it sends no option
 parameter row per sequence, with each sequence's generated tokens kept in a device
 history ring that the kernel itself appends to (the host never builds a penalty
 window, and with pipelined steps the ring already holds the token the host has not
-collected yet).
+collected yet).  min_p, presence / frequency penalty and logit_bias (docs/sampling.md) run
+in the same two launches: a batch that sets one of them uploads 12-wide rows and / or a
+sparse bias operand, every other batch the 8-wide rows it always did.
 """
 from __future__ import annotations
 
@@ -40,6 +42,20 @@ class SamplingParams:
     # token's, and the top_logprobs (0..20) most likely tokens' per generated token
     logprobs: bool = False
     top_logprobs: int = 0
+    # sampler controls (docs/sampling.md): min_p keeps a candidate while p_i >= min_p * p_max;
+    # presence / frequency are subtracted per unique token / per occurrence in the repeat window;
+    # logit_bias {token id: f32} is added to the logits before anything else
+    min_p: float = 0.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Optional[dict] = None
+
+    def __post_init__(self):
+        if self.logit_bias is not None and not isinstance(self.logit_bias, dict):
+            # the wire form (msgpack has no integer-keyed maps in strict mode): [[id, value], ...]
+            self.logit_bias = {int(k): float(v) for k, v in self.logit_bias}
+        if not self.logit_bias:
+            self.logit_bias = None
 
     @classmethod
     def greedy(cls, max_tokens: int = 256, **kw) -> "SamplingParams":
@@ -47,8 +63,9 @@ class SamplingParams:
 
     @classmethod
     def from_ollama(cls, options: Optional[dict], defaults=None, num_predict_default: int = 256) -> "SamplingParams":
-        """Map an Ollama ``options`` dict (temperature, top_k, top_p, repeat_penalty,
-        repeat_last_n, seed, num_predict, stop) onto SamplingParams."""
+        """Map an Ollama ``options`` dict (temperature, top_k, top_p, min_p, repeat_penalty,
+        repeat_last_n, presence_penalty, frequency_penalty, seed, num_predict, stop) onto
+        SamplingParams."""
         o = dict(options or {})
         d = defaults
         sp = cls(
@@ -58,6 +75,9 @@ class SamplingParams:
             repeat_penalty=float(o.get("repeat_penalty", d.repeat_penalty if d else 1.1)),
             repeat_last_n=int(o.get("repeat_last_n", d.repeat_last_n if d else 64)),
             seed=o.get("seed"),
+            min_p=float(o.get("min_p", 0.0)),
+            presence_penalty=float(o.get("presence_penalty", 0.0)),
+            frequency_penalty=float(o.get("frequency_penalty", 0.0)),
         )
         n = int(o.get("num_predict", d.num_predict if d else -1))
         sp.max_tokens = num_predict_default if n is None or n < 0 else n
@@ -68,6 +88,12 @@ class SamplingParams:
     @property
     def is_greedy(self) -> bool:
         return self.temperature <= 0.0 or self.top_k == 1
+
+    @property
+    def reads_ring(self) -> bool:
+        """A repeat, presence or frequency penalty reads the device history ring."""
+        return self.repeat_last_n != 0 and (self.repeat_penalty != 1.0 or self.presence_penalty != 0.0
+                                            or self.frequency_penalty != 0.0)
 
 
 # grammar-constrained rows select over their allowed ids only (LK_SPARSE_SELECT=0: dense
@@ -120,14 +146,35 @@ class Sampler:
         offs = np.cumsum(counts)
         ids = np.concatenate([rows[i] for i in order])
         plan = np.concatenate([flags, offs.astype(np.int32), ids.astype(np.int32)])
+        return self._stage(plan, dev, "_plan")
+
+    def _bias(self, params: list, V: int, dev) -> torch.Tensor:
+        """Device int32 CSR [B+1 offsets | n ids | n f32 values as bits] of the rows' logit_bias
+        (ids outside [0, V) dropped) for ops.sample; staged like :meth:`_plan`."""
+        counts = np.zeros(len(params) + 1, dtype=np.int64)
+        ids, vals = [], []
+        for i, p in enumerate(params):
+            if p.logit_bias:
+                kept = [(int(t), float(v)) for t, v in p.logit_bias.items() if 0 <= int(t) < V]
+                counts[i + 1] = len(kept)
+                ids += [t for t, _ in kept]
+                vals += [v for _, v in kept]
+        csr = np.concatenate([np.cumsum(counts).astype(np.int32), np.asarray(ids, dtype=np.int32),
+                              np.asarray(vals, dtype=np.float32).view(np.int32)])
+        return self._stage(csr, dev, "_bias")
+
+    def _stage(self, plan: np.ndarray, dev, name: str) -> torch.Tensor:
+        """int32 host array -> device tensor through the small pinned ring ``name``."""
         if dev.type != "cuda":
             return torch.from_numpy(plan)
-        ring = getattr(self, "_plan_ring", None)
+        ring = getattr(self, name + "_ring", None)
         if ring is None:
-            ring = self._plan_ring = [[None, None] for _ in range(4)]  # [pinned int32 buffer, event]
-            self._plan_k = 0
-        self._plan_k = (self._plan_k + 1) % len(ring)
-        slot = ring[self._plan_k]
+            ring = [[None, None] for _ in range(4)]  # [pinned int32 buffer, event]
+            setattr(self, name + "_ring", ring)
+            setattr(self, name + "_k", 0)
+        k = (getattr(self, name + "_k") + 1) % len(ring)
+        setattr(self, name + "_k", k)
+        slot = ring[k]
         if slot[1] is not None:
             slot[1].synchronize()  # the copy that last read this buffer has run
         if slot[0] is None or slot[0].numel() < plan.size:
@@ -182,7 +229,11 @@ class Sampler:
         dev = logits.device
         hist, hist_len = self._ring(dev)
         B = logits.shape[0]
-        prm = np.zeros((B, 8), dtype=np.int32)
+        # 12-wide rows (min_p, presence, frequency) and the bias operand only for a batch that
+        # sets one of them: every other batch uploads the 8-wide rows it always did
+        wide = any(p.min_p > 0.0 or p.presence_penalty != 0.0 or p.frequency_penalty != 0.0 for p in params)
+        bias = self._bias(params, logits.shape[1], dev) if any(p.logit_bias for p in params) else None
+        prm = np.zeros((B, 12 if wide else 8), dtype=np.int32)
         f = prm.view(np.float32)
         live = set(keys)
         seed = self.seed
@@ -196,11 +247,15 @@ class Sampler:
             prm[i, 5] = slot
             prm[i, 6] = reset
             prm[i, 7] = (int(p.seed) if p.seed is not None else salt) & 0x7FFFFFFF
+            if wide:
+                f[i, 8], f[i, 9], f[i, 10] = p.min_p, p.presence_penalty, p.frequency_penalty
         prm_t = torch.from_numpy(prm)
         if dev.type == "cuda":
             prm_t = prm_t.pin_memory().to(dev, non_blocking=True)
         lg = logits if logits.dtype == torch.float32 and logits.is_contiguous() else logits.float().contiguous()
-        return ops.sample(lg, prm_t, hist, hist_len, seed)
+        if bias is None:
+            return ops.sample(lg, prm_t, hist, hist_len, seed)
+        return ops.sample(lg, prm_t, hist, hist_len, seed, bias=bias)
 
     # the last call's log-probabilities: None when no row asked, else (rows, n, chosen_lp [R],
     # top_lp [R, n'], top_id [R, n']) -- the requesting batch rows in order, the largest
@@ -246,16 +301,17 @@ class Sampler:
                 allowed = p.logits_processor(histories[i])
                 if allowed is not None:
                     rows[i] = self._as_array(allowed, V)
-        need_filter = any((not p.is_greedy) and (0 < p.top_k < V or p.top_p < 1.0) for p in params)
-        need_penalty = any(p.repeat_penalty != 1.0 and p.repeat_last_n != 0 for p in params)
+        need_filter = any((not p.is_greedy) and (0 < p.top_k < V or p.top_p < 1.0 or p.min_p > 0.0) for p in params)
+        need_penalty = any(p.reads_ring for p in params)
+        need_bias = any(p.logit_bias for p in params)
+        fused = need_filter or need_penalty or need_bias
         plan = None
-        if rows and not need_filter and not need_penalty and SPARSE_SELECT and ops.use_hip(logits):
+        if rows and not fused and SPARSE_SELECT and ops.use_hip(logits):
             # selection straight over each row's allowed ids (HIP select_allowed): no mask
             plan = self._plan(rows, B, dev)
-        if keep and ((rows and plan is None) or need_filter or need_penalty):
+        if keep and ((rows and plan is None) or fused):
             # the dense mask and the penalty kernel edit their input: give them a private copy
             # (the f32 copy the fused sampler would make of bf16 logits anyway, else a clone)
-            fused = need_filter or need_penalty
             logits = logits.float().contiguous() if fused and logits.dtype != torch.float32 else logits.clone()
         if plan is None and rows:
             crow = list(rows)
@@ -265,8 +321,9 @@ class Sampler:
             mask.view(-1).index_fill_(0, idx, 0.0)
             sel = torch.from_numpy(np.asarray(crow, dtype=np.int64)).to(dev, non_blocking=True)
             logits.index_add_(0, sel, mask)
-        if need_filter or need_penalty:
-            # Ollama's chain (penalty -> top-k -> temperature -> top-p -> draw) in one fused kernel
+        if fused:
+            # Ollama's chain (bias -> penalties -> top-k -> temperature -> top-p -> min-p -> draw)
+            # in one fused kernel
             return self._device_sample(logits, params, keys)
         if all(p.is_greedy for p in params):
             if plan is not None:

@@ -308,12 +308,15 @@ def key_to_id(keys):
     return ref.keys_to_ids(keys)
 
 
-def sample(logits, prm, hist, hist_len, seed: int = 0, out=None):
+def sample(logits, prm, hist, hist_len, seed: int = 0, out=None, bias=None):
     """Ollama-default sampling of every row (repeat penalty from the device history ring,
-    top-k, top-p, temperature; greedy rows = argmax); appends the tokens to the ring."""
+    top-k, top-p, temperature; greedy rows = argmax); appends the tokens to the ring.
+    ``prm`` int32 [B, 8], or [B, 12] with min_p, presence and frequency penalty (f32 bits) in
+    columns 8..10; ``bias``: optional int32 CSR [B+1 offsets | n ids | n f32 values as bits] of
+    per-row logit biases (docs/sampling.md)."""
     if use_hip(logits):
-        return lib().sample(logits, prm, hist, hist_len, int(seed) & ((1 << 63) - 1), out)
-    return ref.sample(logits, prm, hist, hist_len, seed)
+        return lib().sample(logits, prm, hist, hist_len, int(seed) & ((1 << 63) - 1), out, bias)
+    return ref.sample(logits, prm, hist, hist_len, seed, bias)
 
 
 def token_logprobs(logits, ids, rows, n: int):

@@ -340,31 +340,61 @@ def repeat_penalty_(logits, window, penalty):
 SAMPLE_KMAX = 1024  # csrc/sampling.hip kSampKMax
 
 
-def sample(logits, prm, hist, hist_len, seed=0):
-    """fp32 reference of lk_sample (csrc/sampling.hip): per row the repeat penalty over the
-    unique tokens of the last min(len, last_n) ring entries, top-k by (value desc, index asc),
-    softmax at the row's temperature, the top-p prefix (a token is kept while the mass before
-    it is <= top_p), one draw; the token is appended to the ring.  Same distribution as the
-    kernel (the random stream differs: torch's generator seeded per (seed, request seed,
+def sample(logits, prm, hist, hist_len, seed=0, bias=None):
+    """fp32 reference of lk_sample (csrc/sampling.hip), rows [B, 8] or [B, 12]: per row the
+    logit bias (``bias``: int32 CSR [B+1 offsets | n ids | n f32 bits], ids outside [0, V)
+    ignored), then over the last min(len, last_n) ring entries each unique token t with c
+    occurrences gets l[t] = rp(l[t]) - (c * frequency + presence) (rp: the repeat penalty),
+    top-k by (value desc, index asc), softmax at the row's temperature, the top-p prefix (a
+    token is kept while the mass before it is <= top_p) cut further to the min-p prefix
+    (p_i >= min_p * p_0), one draw; the token is appended to the ring.  Same distribution as
+    the kernel (the random stream differs: torch's generator seeded per (seed, request seed,
     position))."""
     B, V = logits.shape
     W = hist.shape[1]
     out = torch.empty(B, dtype=torch.int32)
     P = prm.cpu()
+    if P.dim() != 2 or P.shape[0] != B or P.shape[1] not in (8, 12):
+        raise ValueError("prm [B, 8] or [B, 12]")
+    wide = P.shape[1] == 12
+    f32 = torch.float32
+    C = None
+    if bias is not None:
+        C = bias.cpu()
+        if C.dtype != torch.int32 or C.dim() != 1 or C.numel() < B + 1 or C.numel() != B + 1 + 2 * int(C[B]):
+            raise ValueError("bias int32 [B+1 offsets | n ids | n values]")
     for r in range(B):
         row = P[r]
         temp = float(row[0:1].view(torch.float32)[0])
         top_p = float(row[1:2].view(torch.float32)[0])
         pen = float(row[2:3].view(torch.float32)[0])
         top_k, last_n, slot, reset, rseed = (int(x) for x in row[3:8])
+        min_p, presence, frequency = (float(row[i:i + 1].view(f32)[0]) for i in (8, 9, 10)) if wide else (0.0, 0.0, 0.0)
         hl = 0 if reset else int(hist_len[slot])
         l = logits[r].float().clone()
-        if pen != 1.0 and last_n != 0:
+        edited = False
+        if C is not None and int(C[r + 1]) > int(C[r]):
+            nb = int(C[B])
+            for j in range(int(C[r]), int(C[r + 1])):
+                t = int(C[B + 1 + j])
+                if 0 <= t < V:
+                    l[t] = l[t] + C[B + 1 + nb + j: B + 2 + nb + j].view(f32)[0]
+            edited = True
+        if (pen != 1.0 or presence != 0.0 or frequency != 0.0) and last_n != 0:
             n = min(hl, last_n if last_n > 0 else W, W)
-            toks = {int(hist[slot, (hl - 1 - j) % W]) for j in range(n)}
-            for t in toks:
-                if t >= 0:
-                    l[t] = l[t] / pen if l[t] > 0 else l[t] * pen
+            count: dict = {}
+            for j in range(n):
+                t = int(hist[slot, (hl - 1 - j) % W])
+                if 0 <= t < V:
+                    count[t] = count.get(t, 0) + 1
+            for t, c in count.items():
+                x = l[t] / pen if l[t] > 0 else l[t] * pen
+                if presence != 0.0 or frequency != 0.0:
+                    x = x - (torch.tensor(float(c), dtype=f32) * torch.tensor(frequency, dtype=f32)
+                             + torch.tensor(presence, dtype=f32))
+                l[t] = x
+            edited = True
+        if edited:
             logits[r] = l.to(logits.dtype)
         greedy = temp <= 0.0
         K = 1 if greedy else min(top_k if top_k > 0 else SAMPLE_KMAX, V, SAMPLE_KMAX)
@@ -376,6 +406,9 @@ def sample(logits, prm, hist, hist_len, seed=0):
             e = torch.exp((v - v[0]) / temp)
             incl = torch.cumsum(e, 0)
             keep = (incl - e) <= top_p * incl[-1]
+            if min_p > 0.0:
+                keep &= e >= min_p
+                keep[0] = True
             nkeep = int(keep.sum())
             g = torch.Generator().manual_seed((int(seed) * 1000003 + rseed * 7919 + hl) & ((1 << 62) - 1))
             u = float(torch.rand((), generator=g, dtype=torch.float64)) * float(incl[nkeep - 1])

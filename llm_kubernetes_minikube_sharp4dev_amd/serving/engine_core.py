@@ -72,6 +72,12 @@ def sp_to_wire(sp: SamplingParams) -> dict:
     d = {k: getattr(sp, k) for k in SP_FIELDS}
     if sp.logprobs:  # only when asked: every other request's frame is what it always was
         d["logprobs"], d["top_logprobs"] = True, int(sp.top_logprobs)
+    # the sampler controls likewise travel only when set (docs/sampling.md)
+    for k in ("min_p", "presence_penalty", "frequency_penalty"):
+        if getattr(sp, k) != 0.0:
+            d[k] = float(getattr(sp, k))
+    if sp.logit_bias:  # [[id, value], ...]: msgpack maps keep string keys only
+        d["logit_bias"] = [[int(t), float(v)] for t, v in sp.logit_bias.items()]
     return d
 
 

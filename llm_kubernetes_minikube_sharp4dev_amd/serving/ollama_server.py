@@ -108,7 +108,48 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
             raise ValueError("request body must be a JSON object")
         return b
 
+    # ---- sampler controls (docs/sampling.md): ranges per route; a violation raises ValueError
+    # (-> 400) naming the field
+    def _number(v) -> bool:
+        return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+    def check_ollama_controls(options) -> None:
+        o = options if isinstance(options, dict) else {}
+        if "min_p" in o and not (_number(o["min_p"]) and 0.0 <= o["min_p"] <= 1.0):
+            raise ValueError("min_p must be a number between 0 and 1")
+        for k in ("presence_penalty", "frequency_penalty"):
+            if k in o and not _number(o[k]):
+                raise ValueError(f"{k} must be a finite number")
+
+    def set_openai_controls(sp: SamplingParams, b: dict, h) -> SamplingParams:
+        """``presence_penalty`` / ``frequency_penalty`` ([-2, 2]) and ``logit_bias`` (at most 300
+        entries, canonical decimal token id -> [-100, 100]) of an OpenAI request body."""
+        for k in ("presence_penalty", "frequency_penalty"):
+            v = b.get(k)
+            if v is None:
+                continue
+            if not (_number(v) and -2.0 <= v <= 2.0):
+                raise ValueError(f"{k} must be a number between -2 and 2")
+            setattr(sp, k, float(v))
+        lb = b.get("logit_bias")
+        if lb is None:
+            return sp
+        if not isinstance(lb, dict) or len(lb) > 300:
+            raise ValueError("logit_bias must be an object of at most 300 entries")
+        model = getattr(h.engine, "model", None)
+        vocab = int(model.cfg.vocab_size) if model is not None else int(getattr(h.engine, "vocab_size", 0))
+        bias = {}
+        for k, v in lb.items():
+            if not (k.isascii() and k.isdigit() and str(int(k)) == k and int(k) < vocab):
+                raise ValueError(f"logit_bias key {k!r} must be a token id between 0 and {vocab - 1}")
+            if not (_number(v) and -100.0 <= v <= 100.0):
+                raise ValueError(f"logit_bias value for {k!r} must be a number between -100 and 100")
+            bias[int(k)] = float(v)
+        sp.logit_bias = bias or None
+        return sp
+
     def params_for(b: dict, h) -> SamplingParams:
+        check_ollama_controls(b.get("options"))
         sp = SamplingParams.from_ollama(b.get("options"), mgr.cfg.engine, mgr.cfg.engine.default_max_new_tokens)
         fmt = b.get("format")
         if fmt:
@@ -521,6 +562,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
                                         mgr.cfg.engine.default_max_new_tokens)
         try:
             set_logprobs(sp, bool(b.get("logprobs")), b.get("top_logprobs"))
+            set_openai_controls(sp, b, h)
         except ValueError as e:
             return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
         seq = await h.async_engine.generate(ids, sp)
@@ -545,6 +587,10 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         ids = h.tokenizer.encode(b.get("prompt") or "", add_bos=True)
         sp = SamplingParams.from_ollama({"temperature": b.get("temperature", 1.0),
                                          "num_predict": b.get("max_tokens") or 16}, mgr.cfg.engine)
+        try:
+            set_openai_controls(sp, b, h)
+        except ValueError as e:
+            return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
         n_lp = b.get("logprobs")  # the legacy integer: the number of alternatives per token
         try:
             if isinstance(n_lp, bool):

@@ -246,6 +246,7 @@ class _EngineView:
     max_model_len: int
     eos_ids: set
     model: Optional[object] = None
+    vocab_size: int = 0  # the core's model vocabulary (logit_bias ids are checked against it)
 
 
 @dataclass
@@ -342,7 +343,8 @@ class RemoteModelManager(ModelManager):
                 raise KeyError(f"model '{name}' does not support generate")
             meta = self._load_remote(name)
             ck = self.checkpoints.get(name) or self.checkpoints.get(preset)
-            h = RemoteGeneratorHandle(name, preset, _EngineView(meta["max_model_len"], set(meta["eos_ids"])),
+            h = RemoteGeneratorHandle(name, preset, _EngineView(meta["max_model_len"], set(meta["eos_ids"]),
+                                                                vocab_size=int(meta.get("vocab_size") or 0)),
                                       _RemoteAsync(self.pool, name, self.cfg.agent.request_timeout_s),
                                       load_tokenizer(ck), meta["chat_style"], load_s=meta["load_s"],
                                       tp=int(meta.get("tp", 1)))
