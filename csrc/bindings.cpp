@@ -835,6 +835,31 @@ std::vector<at::Tensor> token_logprobs(const at::Tensor& logits, const at::Tenso
   return {chosen, top_lp, top_id};
 }
 
+// Token masks of schema-constrained rows (csrc/token_mask.hip lk_mask_logits): see kernels.h
+at::Tensor mask_logits(const at::Tensor& logits, const at::Tensor& pool, const at::Tensor& mask_row,
+                       const c10::optional<at::Tensor>& out_) {
+  CHECK_CUDA(logits); CHECK_LASTDIM(logits); CHECK_CUDA(pool); CHECK_I32(pool); CHECK_CONTIG(pool);
+  CHECK_CUDA(mask_row); CHECK_I32(mask_row); CHECK_CONTIG(mask_row);
+  TORCH_CHECK(logits.dim() == 2, "logits [B, V]");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or f32");
+  TORCH_CHECK(logits.size(0) <= 65535 && logits.size(1) < (1ll << 30), "logits [B <= 65535, V < 2^30]");
+  const int B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B == 0 || (V >= 1 && logits.stride(0) >= V), "logits row stride");
+  TORCH_CHECK(pool.dim() == 2 && pool.size(0) < (1ll << 31) && pool.size(1) < (1ll << 31), "pool [R, words] int32");
+  TORCH_CHECK(mask_row.dim() == 1 && mask_row.numel() >= B, "mask_row [B]");
+  at::Tensor out = out_ ? *out_ : at::empty({B, V}, logits.options().dtype(at::kFloat));
+  CHECK_CUDA(out); CHECK_F32(out); CHECK_LASTDIM(out);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) == V && (B == 0 || out.stride(0) >= V), "out f32 [B, V]");
+  if (B > 0 && out.data_ptr() == logits.data_ptr())
+    TORCH_CHECK(!is_bf16 && out.stride(0) == logits.stride(0), "in place needs f32 logits and equal row strides");
+  int rc = lk_mask_logits(logits.data_ptr(), is_bf16 ? 1 : 0, logits.stride(0), out.data_ptr<float>(), out.stride(0), B, V,
+                          reinterpret_cast<const unsigned*>(pool.data_ptr<int>()), (int)pool.size(0), (int)pool.size(1),
+                          ip(mask_row), cur_stream());
+  CHECK_RC(rc, "mask_logits");
+  return out;
+}
+
 void repeat_penalty_(at::Tensor& logits, const at::Tensor& window, const at::Tensor& penalty) {
   CHECK_CUDA(logits); CHECK_I32(window); CHECK_F32(penalty); CHECK_CONTIG(window);
   const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
@@ -1081,6 +1106,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("select_tokens", &select_tokens, "", py::arg("logits"), py::arg("temps") = py::none(), py::arg("seed") = 0, py::arg("step") = 0, py::arg("out") = py::none());
   m.def("repeat_penalty_", &repeat_penalty_);
   m.def("token_logprobs", &token_logprobs, "", py::arg("logits"), py::arg("ids"), py::arg("rows"), py::arg("n"));
+  m.def("mask_logits", &mask_logits, "", py::arg("logits"), py::arg("pool"), py::arg("mask_row"), py::arg("out") = py::none());
   m.def("sample", &sample, "", py::arg("logits"), py::arg("prm"), py::arg("hist"), py::arg("hist_len"),
         py::arg("seed") = 0, py::arg("out") = py::none(), py::arg("bias") = py::none());
 }

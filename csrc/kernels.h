@@ -209,6 +209,16 @@ int lk_sample(float* logits, long ls, int B, int V, const int* prm, int pw, cons
 int lk_token_logprobs(const void* logits, int is_bf16, long ls, int B, int V, const int* rows, int R,
                       const int* ids, int n, float* chosen_lp, float* top_lp, int* top_id, hipStream_t st);
 
+// token_mask.hip
+// Token masks of schema-constrained rows: dst[b][v] = f32(src[b][v]) (bit-exact) where
+// mask_row[b] < 0 or bit v & 31 of pool[mask_row[b] * words + (v >> 5)] is set, else -inf, for
+// b < B, v < V.  src: bf16 or f32 [B, >= V], row stride ls; dst: f32, row stride ld (columns
+// [V, ld) are not written; dst == src is allowed for f32 with ld == ls).  pool: R rows of
+// `words` = (V + 31) / 32 words (anything else: -1); mask_row[b] >= R masks the whole row and
+// reads nothing.  One launch, grid (ceil(V / 2048), B); B <= 0 launches nothing.
+int lk_mask_logits(const void* src, int is_bf16, long ls, float* dst, long ld, int B, int V, const unsigned* pool, int R,
+                   int words, const int* mask_row, hipStream_t st);
+
 // csrc/marker.hip: a one-wave marker kernel bounding a timed window in kernel traces
 int lk_window_mark(int id, hipStream_t st);
 // a launch the runtime rejects (2048 threads): returns the LK_CHECK_LAUNCH code, runs nothing

@@ -192,9 +192,16 @@ class JsonGrammar:
 
 
 def json_logits_processor(tok, schema: Optional[dict] = None):
-    """``format: "json"`` / schema -> a JSON constraint (schema keys are not enforced
-    beyond syntactic validity)."""
-    return JsonGrammar(tok)
+    """``format: "json"`` (``schema`` None) -> any syntactically valid JSON value
+    (:class:`JsonGrammar`); a JSON schema -> a per-request cursor over the compiled, shared
+    :class:`~.schema_grammar.SchemaGrammar`, whose calls return ``TokenMask`` objects
+    (docs/structured_outputs.md).  Raises ``ValueError`` naming the keyword for a schema
+    outside the supported subset."""
+    if schema is None:
+        return JsonGrammar(tok)
+    from .schema_grammar import compiled
+
+    return compiled(tok, schema).cursor()
 
 
 # ----------------------------------------------------------------------------- tool calls

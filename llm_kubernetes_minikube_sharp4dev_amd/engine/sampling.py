@@ -11,6 +11,12 @@ window, and with pipelined steps the ring already holds the token the host has n
 collected yet).  min_p, presence / frequency penalty and logit_bias (docs/sampling.md) run
 in the same two launches: a batch that sets one of them uploads 12-wide rows and / or a
 sparse bias operand, every other batch the 8-wide rows it always did.
+
+Rows whose processor returns a ``TokenMask`` (JSON-schema decoding, docs/structured_outputs.md)
+are constrained on the device: the masks live in a lazily created pool of bitmask rows, a step
+uploads only the masks the pool does not hold plus one row index per batch row, and one
+``ops.mask_logits`` launch writes the masked f32 copy of the logits that the batch's selector
+then reads.  A batch without such a row runs the code it always did.
 """
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .schema_grammar import TokenMask
 
 
 @dataclass
@@ -167,6 +174,16 @@ class Sampler:
         """int32 host array -> device tensor through the small pinned ring ``name``."""
         if dev.type != "cuda":
             return torch.from_numpy(plan)
+        src, slot = self._pinned(plan, name)
+        out = torch.empty(plan.size, dtype=torch.int32, device=dev)
+        out.copy_(src, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return out
+
+    def _pinned(self, plan: np.ndarray, name: str):
+        """``plan`` copied into the next buffer of the pinned ring ``name`` -> (pinned view, ring
+        slot); the caller records ``slot[1]`` behind its last copy out of the view."""
         ring = getattr(self, name + "_ring", None)
         if ring is None:
             ring = [[None, None] for _ in range(4)]  # [pinned int32 buffer, event]
@@ -180,11 +197,60 @@ class Sampler:
         if slot[0] is None or slot[0].numel() < plan.size:
             slot[0] = torch.empty(max(2 * plan.size, 1 << 14), dtype=torch.int32, pin_memory=True)
         slot[0][: plan.size].numpy()[:] = plan
-        out = torch.empty(plan.size, dtype=torch.int32, device=dev)
-        out.copy_(slot[0][: plan.size], non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record()
-        return out
+        return slot[0][: plan.size], slot
+
+    # ---------------------------------------------------------------- device token-mask pool
+    MASK_ROWS = 1024  # bitmask rows of the pool (16 MB at V = 128,256), LRU-evicted beyond
+
+    def _mask_pool(self, dev, words: int) -> torch.Tensor:
+        """int32 [MASK_ROWS, words] on ``dev``, created on the first TokenMask this sampler sees
+        there (a server that never gets a schema allocates nothing)."""
+        pool = getattr(self, "_mpool", None)
+        if pool is None or pool.device != dev or pool.shape[1] != words:
+            pool = self._mpool = torch.zeros((self.MASK_ROWS, words), dtype=torch.int32, device=dev)
+            self._mrow_of: dict = {}  # id(mask) -> [mask, pool row, last step used] (the reference keeps the id valid)
+            self._mfree = list(range(self.MASK_ROWS - 1, -1, -1))
+        return pool
+
+    def _mask_rows(self, masks: dict, B: int, V: int, dev):
+        """(pool, device int32 [B] pool row per batch row, -1 = no mask) for the batch rows
+        ``masks`` {row: TokenMask}.  Only masks the pool does not hold are uploaded: padded or
+        truncated to ``V`` bits, staged through a pinned ring and copied into their rows without
+        blocking -- stream order keeps a row that an earlier step still reads intact.  A new mask
+        takes a free row or the least recently used one that this batch does not use."""
+        words = (V + 31) // 32
+        pool = self._mask_pool(dev, words)
+        live = {id(m) for m in masks.values()}
+        if len(live) > self.MASK_ROWS:
+            raise RuntimeError(f"{len(live)} distinct token masks in one batch; the pool holds {self.MASK_ROWS}")
+        mrow = np.full(B, -1, dtype=np.int32)
+        new = []
+        for i, m in masks.items():
+            ent = self._mrow_of.get(id(m))
+            if ent is None:
+                if self._mfree:
+                    row = self._mfree.pop()
+                else:
+                    victim = min((k for k in self._mrow_of if k not in live), key=lambda k: self._mrow_of[k][2])
+                    row = self._mrow_of.pop(victim)[1]
+                ent = self._mrow_of[id(m)] = [m, row, self.step]
+                w = m.words[:words] if m.words.size >= words else np.concatenate(
+                    [m.words, np.zeros(words - m.words.size, dtype=np.uint32)])
+                new.append((row, w))
+            ent[2] = self.step
+            mrow[i] = ent[1]
+        if new:
+            host = np.concatenate([w for _, w in new]).view(np.int32)
+            if dev.type != "cuda":
+                src, slot = torch.from_numpy(host.copy()), None
+            else:
+                src, slot = self._pinned(host, "_mask")
+            for j, (row, _) in enumerate(new):
+                pool[row].copy_(src[j * words:(j + 1) * words], non_blocking=True)
+            if slot is not None:
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+        return pool, self._stage(mrow, dev, "_mrow")
 
     # ---------------------------------------------------------------- device sampler state
     RING = 256        # default history window per sequence (repeat_last_n is clamped to it)
@@ -295,12 +361,22 @@ class Sampler:
         # scalar, mask[r, t] = 0.0, blocks the host until the device queue drains --
         # measured 15 ms behind a queued forward -- serialising the step pipelining.)
         V = logits.shape[1]
-        rows = {}
+        rows, masks = {}, {}
         for i, p in enumerate(params):
             if p.logits_processor is not None:
                 allowed = p.logits_processor(histories[i])
-                if allowed is not None:
+                if isinstance(allowed, TokenMask):
+                    masks[i] = allowed
+                elif allowed is not None:
                     rows[i] = self._as_array(allowed, V)
+        if masks:
+            # schema rows (docs/structured_outputs.md): one launch writes a private f32 copy of
+            # the logits with every id outside a row's bitmask at -inf -- the copy the fused
+            # sampler makes of bf16 logits anyway -- and the batch goes on to the selector it
+            # would have used; rows with id lists are handled on that copy as they always were
+            pool, mrow = self._mask_rows(masks, B, V, dev)
+            logits = ops.mask_logits(logits, pool, mrow)
+            keep = False  # the copy is ours to edit
         need_filter = any((not p.is_greedy) and (0 < p.top_k < V or p.top_p < 1.0 or p.min_p > 0.0) for p in params)
         need_penalty = any(p.reads_ring for p in params)
         need_bias = any(p.logit_bias for p in params)

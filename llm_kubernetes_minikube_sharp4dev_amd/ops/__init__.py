@@ -329,6 +329,17 @@ def token_logprobs(logits, ids, rows, n: int):
     return ref.token_logprobs(logits, ids, rows, n)
 
 
+def mask_logits(logits, pool, mask_row, out=None):
+    """Token masks of schema-constrained rows (docs/structured_outputs.md): an f32 copy of
+    ``logits`` [B, V] (bf16 or f32, never modified unless ``out`` is ``logits``) in which every id
+    outside its row's allowed set is ``-inf``.  ``pool`` int32 [R, ceil(V / 32)] holds one bitmask
+    per row (bit ``v & 31`` of word ``v >> 5`` = id ``v``), ``mask_row`` int32 [B] each batch
+    row's pool row (< 0: unconstrained; >= R: the whole row masked).  One launch for the batch."""
+    if use_hip(logits):
+        return lib().mask_logits(logits, pool, mask_row, out)
+    return ref.mask_logits(logits, pool, mask_row, out)
+
+
 def repeat_penalty_(logits, window, penalty):
     if use_hip(logits):
         lib().repeat_penalty_(logits, window, penalty)

@@ -325,6 +325,30 @@ def token_logprobs(logits, ids, rows, n: int):
     return chosen, lp.gather(1, order), order.int()
 
 
+def mask_logits(logits, pool, mask_row, out=None):
+    """fp32 reference of lk_mask_logits (csrc/token_mask.hip): ``out[b, v] = f32(logits[b, v])``
+    (bit-exact) where ``mask_row[b] < 0`` or bit ``v & 31`` of ``pool[mask_row[b], v >> 5]`` is
+    set, else ``-inf``; a ``mask_row[b] >= R`` masks the whole row.  ``pool`` int32 [R, words]
+    with ``words == ceil(V / 32)`` (anything else raises); ``out``: optional f32 [B, V] view."""
+    B, V = logits.shape
+    R, words = pool.shape
+    if words != (V + 31) // 32:
+        raise ValueError(f"mask_logits: pool rows of {words} words for V = {V} (need {(V + 31) // 32})")
+    mr = mask_row[:B].long()
+    v = torch.arange(V, device=logits.device)
+    if R > 0:
+        w = pool.index_select(0, mr.clamp(0, R - 1))[:, v >> 5]
+        bit = ((w >> (v & 31).to(w.dtype)[None]) & 1) != 0
+    else:
+        bit = torch.zeros((B, V), dtype=torch.bool, device=logits.device)
+    keep = (bit & (mr < R)[:, None]) | (mr < 0)[:, None]
+    res = torch.where(keep, logits.float(), torch.full((), float("-inf"), device=logits.device))
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 def repeat_penalty_(logits, window, penalty):
     for b in range(logits.shape[0]):
         p = float(penalty[b])

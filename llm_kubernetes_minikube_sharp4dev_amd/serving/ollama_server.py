@@ -160,6 +160,34 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         # Ollama puts these at the request's top level, not in options
         return set_logprobs(sp, bool(b.get("logprobs")), b.get("top_logprobs"))
 
+    def set_response_format(sp: SamplingParams, rf, h) -> SamplingParams:
+        """OpenAI ``response_format`` (docs/structured_outputs.md): absent / ``text`` = free
+        text, ``json_object`` = any JSON value, ``json_schema`` = the schema enforced.  Sets
+        ``sp.format`` like the Ollama routes do, so a remote engine core rebuilds the processor."""
+        if rf is None:
+            return sp
+        kind = rf.get("type") if isinstance(rf, dict) else None
+        if kind == "text":
+            return sp
+        if kind == "json_object":
+            fmt = "json"
+        elif kind == "json_schema":
+            js = rf.get("json_schema")
+            fmt = js.get("schema") if isinstance(js, dict) else None
+            if not isinstance(fmt, dict):
+                raise ValueError("response_format.json_schema.schema must be a JSON schema object")
+            fmt = fmt or "json"  # the empty schema is any JSON value (and {} is "no format" on the wire)
+        else:
+            raise ValueError("response_format.type must be 'text', 'json_object' or 'json_schema'")
+        from ..engine.constrained import json_logits_processor
+
+        try:
+            sp.logits_processor = json_logits_processor(h.tokenizer, fmt if isinstance(fmt, dict) else None)
+        except ValueError as e:
+            raise ValueError(f"response_format.json_schema.schema: {e}")
+        sp.format = fmt
+        return sp
+
     # ---- token log-probabilities (docs/logprobs.md): request fields -> SamplingParams, engine
     # entries (chosen logprob, [(id, logprob), ...]) -> OpenAI-shaped JSON entries
     def set_logprobs(sp: SamplingParams, want, top) -> SamplingParams:
@@ -563,6 +591,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         try:
             set_logprobs(sp, bool(b.get("logprobs")), b.get("top_logprobs"))
             set_openai_controls(sp, b, h)
+            set_response_format(sp, b.get("response_format"), h)
         except ValueError as e:
             return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
         seq = await h.async_engine.generate(ids, sp)
