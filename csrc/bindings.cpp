@@ -714,6 +714,34 @@ at::Tensor pool_normalize(const at::Tensor& hidden, const at::Tensor& cu, int64_
   return out;
 }
 
+// cross-encoder score head over the CLS rows of packed hidden states -> f32 [B] (activation 0: the
+// logit, 1: its sigmoid); pool_w [H, H] (row = output), cls_w [H] or [1, H]
+at::Tensor rerank_head(const at::Tensor& hidden, const at::Tensor& cu, const at::Tensor& pool_w,
+                       const c10::optional<at::Tensor>& pool_b, const at::Tensor& cls_w,
+                       const c10::optional<at::Tensor>& cls_b, int64_t activation) {
+  CHECK_CUDA(hidden); CHECK_BF16(hidden); CHECK_LASTDIM(hidden); CHECK_CUDA(cu); CHECK_I32(cu); CHECK_CONTIG(cu);
+  TORCH_CHECK(hidden.dim() == 2, "hidden must be [T, H]");
+  TORCH_CHECK(cu.numel() >= 1, "cu must be [B+1]");
+  const int B = cu.numel() - 1, H = hidden.size(1);
+  TORCH_CHECK(H > 0 && H % 8 == 0, "rerank_head: H must be a multiple of 8 (got ", H, ")");
+  TORCH_CHECK(H <= 1024, "rerank_head: H must be at most 1024 (got ", H, ")");
+  TORCH_CHECK(hidden.size(0) <= 1 || hidden.stride(0) >= H, "rerank_head: hidden row stride ", hidden.stride(0),
+              " is smaller than H ", H);
+  check_rows16(hidden, "hidden");
+  CHECK_CUDA(pool_w); CHECK_BF16(pool_w); CHECK_CONTIG(pool_w); check_rows16(pool_w, "pool_w");
+  TORCH_CHECK(pool_w.dim() == 2 && pool_w.size(0) == H && pool_w.size(1) == H, "pool_w must be [H, H]");
+  CHECK_CUDA(cls_w); CHECK_BF16(cls_w); CHECK_CONTIG(cls_w); check_rows16(cls_w, "cls_w");
+  TORCH_CHECK(cls_w.numel() == H, "cls_w must hold H values");
+  if (pool_b) { CHECK_CUDA(*pool_b); CHECK_BF16(*pool_b); CHECK_CONTIG(*pool_b); TORCH_CHECK(pool_b->numel() == H, "pool_b must be [H]"); check_rows16(*pool_b, "pool_b"); }
+  if (cls_b) { CHECK_CUDA(*cls_b); CHECK_BF16(*cls_b); TORCH_CHECK(cls_b->numel() == 1, "cls_b must be [1]"); }
+  TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (logit) or 1 (sigmoid)");
+  at::Tensor out = at::empty({B}, hidden.options().dtype(at::kFloat));
+  int rc = lk_rerank_head(bp(hidden), hidden.size(0) <= 1 ? (long)H : hidden.stride(0), ip(cu), B, H, bp(pool_w),
+                          bpo(pool_b), bp(cls_w), bpo(cls_b), (int)activation, out.data_ptr<float>(), cur_stream());
+  CHECK_RC(rc, "rerank_head");
+  return out;
+}
+
 at::Tensor row_norms(const at::Tensor& x) {
   CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
   at::Tensor out = at::empty({x.size(0)}, x.options().dtype(at::kFloat));
@@ -1100,6 +1128,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_merge", &knn_merge);
   m.def("pool_normalize", &pool_normalize, "", py::arg("hidden"), py::arg("cu"), py::arg("mode"), py::arg("normalize"),
         py::arg("out") = py::none());
+  m.def("rerank_head", &rerank_head, "", py::arg("hidden"), py::arg("cu"), py::arg("pool_w"), py::arg("pool_b"),
+        py::arg("cls_w"), py::arg("cls_b"), py::arg("activation") = 0);
   m.def("row_norms", &row_norms);
   m.def("select_allowed", &select_allowed, "", py::arg("logits"), py::arg("plan"), py::arg("temps") = py::none(),
         py::arg("seed") = 0, py::arg("step") = 0);

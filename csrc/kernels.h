@@ -180,6 +180,13 @@ int lk_pool_normalize(const bf16_t* hidden, long hs, const int* cu, int B, int H
                       int normalize, void* out, long os, int out_bf16, hipStream_t st);
 int lk_row_norms(const bf16_t* x, long N, int D, float* out, hipStream_t st);
 
+// rerank.hip
+// cross-encoder score head: CLS row -> pool_w [H,H] (+pool_b) -> tanh -> cls_w [H] (+cls_b) -> out [B]
+// f32 (activation 0 logit, 1 sigmoid); H % 8 == 0, H <= 1024, hs >= H
+int lk_rerank_head(const bf16_t* hidden, long hs, const int* cu, int B, int H, const bf16_t* pool_w,
+                   const bf16_t* pool_b, const bf16_t* cls_w, const bf16_t* cls_b, int activation, float* out,
+                   hipStream_t st);
+
 // sampling.hip
 // plan: int32 [B flags | B+1 offsets | allowed ids] (ids in [0, V), checked by the caller)
 int lk_select_allowed(const void* logits, int is_bf16, long ls, int B, int V, const float* temps,

@@ -318,6 +318,17 @@ def _backends(args, cfg, mgr=None):
     return emb, llm, k8s
 
 
+def _rag_reranker(cfg, mgr=None):
+    """The /rag/search second stage (``rag.rerank_model``; None when it is not configured)."""
+    if not cfg.rag.rerank_model:
+        return None
+    from .rag.reranker import HttpReranker, LocalReranker
+
+    if mgr is not None:
+        return LocalReranker(mgr.reranker(cfg.rag.rerank_model).engine)
+    return HttpReranker(cfg.agent.embedder_url, cfg.rag.rerank_model)
+
+
 def cmd_rag_app(args):
     from .apps.rag_app import create_rag_app
     from .rag.index import RagIndex
@@ -336,10 +347,10 @@ def cmd_rag_app(args):
     try:
         if args.synthetic_docs:
             idx = _synthetic_index(args, emb)
-            app = create_rag_app(cfg, idx, llm, k8s, build_index=False)
+            app = create_rag_app(cfg, idx, llm, k8s, build_index=False, reranker=_rag_reranker(cfg))
         else:
             idx = RagIndex(emb, backend=cfg.rag.index_backend, device=_index_device(args, group))
-            app = create_rag_app(cfg, idx, llm, k8s)
+            app = create_rag_app(cfg, idx, llm, k8s, reranker=_rag_reranker(cfg))
         if group is not None:
             _shard_served_index(idx, group)
             _serve_apps([(app, args.port)], args.host)
@@ -502,7 +513,7 @@ def cmd_all(args):
             mgr.generator(cfg.agent.gen_model)  # the followers are building it
         emb, llm, k8s = _backends(args, cfg, mgr)
         idx = RagIndex(emb, backend=cfg.rag.index_backend, device=_index_device(args, None) if dev is None else str(dev))
-        rag = create_rag_app(cfg, idx, llm, k8s)
+        rag = create_rag_app(cfg, idx, llm, k8s, reranker=_rag_reranker(cfg, mgr))
         if tp is not None:
             _shard_served_index(idx, mgr.generator(cfg.agent.gen_model).engine)
         apps = [(create_app(mgr), cfg.server.ollama_port), (rag, cfg.server.rag_port),

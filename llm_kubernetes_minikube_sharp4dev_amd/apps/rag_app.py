@@ -35,7 +35,10 @@ from .common import BindError, NetJSONResponse, add_https_redirection, bind_body
 log = get_logger("RAG.Search")
 
 
-def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None, build_index: bool = True):
+def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None, build_index: bool = True,
+                   reranker=None):
+    """``reranker``: the second stage of /rag/search (``score(query, docs)``, :mod:`..rag.reranker`),
+    used only when ``cfg.rag.rerank_model`` is set."""
     from fastapi import FastAPI, Request
     from starlette.responses import Response
 
@@ -43,6 +46,9 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
     r = cfg.rag
     app = FastAPI(title="Minimal_RAG (MI355X)")
     app.state.cfg, app.state.index, app.state.llm, app.state.k8s = cfg, index, llm, k8s
+    if r.rerank_model and reranker is None:
+        raise ValueError(f"rag.rerank_model is '{r.rerank_model}' but no reranker was given to the RAG app")
+    app.state.reranker = reranker if r.rerank_model else None
     tracer = Tracer("rag_app")
     app.state.tracer = tracer
     if build_index and index is not None and len(index) == 0:
@@ -80,6 +86,10 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
     async def health():
         return NetJSONResponse({"status": "ok"})
 
+    def _rr(h) -> dict:  # (absent without a reranker: the response is unchanged)
+        rs = getattr(h, "rerank_score", None)
+        return {} if rs is None else {"rerankScore": rs}
+
     @app.post("/rag/search")
     async def rag_search(request: Request):
         t0 = time.perf_counter()
@@ -93,7 +103,10 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
             return NetJSONResponse({"error": "Query vuota"}, status_code=400)
         k = r.search_default_topk if top_k is None else min(max(top_k, r.search_topk_min), r.search_topk_max)
         with tracer.span("rag.search", k=k):
-            hits = await asyncio.to_thread(index.query, query, k)
+            if app.state.reranker is None:
+                hits = await asyncio.to_thread(index.query, query, k)
+            else:  # opt-in second stage: the best k of the cosine candidates, in rerank order
+                hits = await asyncio.to_thread(index.query, query, k, app.state.reranker, r.rerank_candidates)
         if not hits:
             return NetJSONResponse({"info": "Nessun risultato. L'indice potrebbe essere vuoto.", "results": []})
         best = max(h.score for h in hits)
@@ -102,11 +115,11 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
         if best < r.search_min_score:
             return NetJSONResponse({
                 "info": f"Best score basso ({net_num(best)}). Aggiungi runbook più pertinenti o verifica l'indice.",
-                "results": [{"id": h.id, "source": h.source, "score": h.score} for h in hits]})
+                "results": [{"id": h.id, "source": h.source, "score": h.score, **_rr(h)} for h in hits]})
         out = []
         for h in hits:
             prev = u16slice(h.text, 0, r.preview_chars) + "..." if u16len(h.text) > r.preview_chars else h.text
-            out.append({"id": h.id, "source": h.source, "score": h.score, "preview": prev})
+            out.append({"id": h.id, "source": h.source, "score": h.score, **_rr(h), "preview": prev})
         return NetJSONResponse(out)
 
     @app.post("/agent_rag")

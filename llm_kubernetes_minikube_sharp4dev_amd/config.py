@@ -44,6 +44,8 @@ class RagConfig:
     embed_model: str = "nomic-embed-text"              # Program.cs:18
     index_backend: str = "auto"                        # auto | exact (cpu f64) | gpu (HIP kNN)
     cache_dir: str = ""                                # persisted embeddings (checkpoint/resume)
+    rerank_model: Optional[str] = None                 # /rag/search second stage (off unless set)
+    rerank_candidates: int = 24                        # cosine hits handed to the reranker
 
 
 @dataclass
@@ -134,6 +136,8 @@ class ModelPresets:
         "minilm": "minilm-l6",
         "bert-tiny": "bert-tiny",
     })
+    # cross-encoder rerankers (POST /v1/rerank): client-side name -> models.configs.RERANKERS preset
+    rerankers: dict = field(default_factory=lambda: {"ms-marco-minilm-l6": "ms-marco-minilm-l6"})
 
 
 @dataclass

@@ -7,8 +7,9 @@ from typing import Optional
 import torch
 
 from ..parallel.tp import SINGLE, TPGroup
-from .bert import EncoderModel
-from .configs import DECODERS, ENCODERS, DecoderConfig, EncoderConfig, decoder_config, encoder_config
+from .bert import CrossEncoderModel, EncoderModel
+from .configs import (DECODERS, ENCODERS, RERANKERS, DecoderConfig, EncoderConfig, decoder_config, encoder_config,
+                      reranker_config)
 from . import llama
 from .llama import LlamaModel
 from .opt import OPTModel
@@ -50,5 +51,16 @@ def build_encoder(name: str | EncoderConfig, device="cpu", dtype=torch.bfloat16,
     return m.eval()
 
 
-__all__ = ["build_decoder", "build_encoder", "DECODERS", "ENCODERS", "DecoderConfig", "EncoderConfig",
-           "LlamaModel", "OPTModel", "EncoderModel"]
+def build_reranker(name: str | EncoderConfig, device="cpu", dtype=torch.bfloat16, seed: int = 0,
+                   checkpoint: Optional[str] = None, **overrides):
+    cfg = name if isinstance(name, EncoderConfig) else reranker_config(name, **overrides)
+    m = CrossEncoderModel(cfg, dtype, device)
+    if checkpoint:
+        m.load_hf_state_dict(_load_safetensors_dir(checkpoint))
+    else:
+        m.random_init(seed)
+    return m.eval()
+
+
+__all__ = ["build_decoder", "build_encoder", "build_reranker", "DECODERS", "ENCODERS", "RERANKERS", "DecoderConfig",
+           "EncoderConfig", "LlamaModel", "OPTModel", "EncoderModel", "CrossEncoderModel"]

@@ -139,3 +139,46 @@ class EncoderModel(nn.Module):
             L.ln2_w.copy_(t(p + "output.LayerNorm.weight"))
             L.ln2_b.copy_(t(p + "output.LayerNorm.bias"))
         return self
+
+
+class CrossEncoderModel(EncoderModel):
+    """BERT cross-encoder (``BertForSequenceClassification`` with one label): the encoder over a
+    packed ``[CLS] query [SEP] document [SEP]`` pair, then the score head on the CLS row --
+    pooler dense + tanh -> classifier -> one logit per pair (``ops.rerank_head``, one kernel)."""
+
+    def __init__(self, cfg: EncoderConfig, dtype=torch.bfloat16, device="cpu"):
+        super().__init__(cfg, dtype, device)
+        H = cfg.hidden
+        e = dict(dtype=dtype, device=device)
+        self.pool_w = nn.Parameter(torch.empty(H, H, **e), requires_grad=False)
+        self.pool_b = nn.Parameter(torch.zeros(H, **e), requires_grad=False)
+        # (random_init draws every parameter whose name does not end in ``_b``: cls_w gets the
+        # common std, so random models give distinct scores)
+        self.cls_w = nn.Parameter(torch.empty(1, H, **e), requires_grad=False)
+        self.cls_b = nn.Parameter(torch.zeros(1, **e), requires_grad=False)
+
+    def forward(self, ids: torch.Tensor, cu: torch.Tensor, positions: torch.Tensor, lens_cpu: list,
+                type_ids=None, activation: int = 0, tiles=None):
+        """Packed pairs -> f32 [B] scores (``activation`` 0: logits, 1: sigmoid of the logit)."""
+        h = super().forward(ids, cu, positions, lens_cpu, type_ids=type_ids, pool=False, tiles=tiles)
+        return ops.rerank_head(h, cu, self.pool_w, self.pool_b, self.cls_w, self.cls_b, activation)
+
+    @torch.no_grad()
+    def load_hf_state_dict(self, sd: dict):
+        """HuggingFace ``BertForSequenceClassification`` names (``num_labels`` must be 1)."""
+        cw = sd["classifier.weight"]
+        if cw.dim() != 2 or cw.shape[0] != 1:
+            raise ValueError(f"cross-encoder needs num_labels == 1: classifier.weight has shape {tuple(cw.shape)}")
+        super().load_hf_state_dict(sd)
+
+        def t(n):
+            for k in ("bert." + n, n):
+                if k in sd:
+                    return sd[k].to(self.dtype)
+            raise KeyError(n)
+
+        self.pool_w.copy_(t("pooler.dense.weight"))
+        self.pool_b.copy_(t("pooler.dense.bias"))
+        self.cls_w.copy_(cw.to(self.dtype))
+        self.cls_b.copy_(sd["classifier.bias"].to(self.dtype).reshape(1))
+        return self

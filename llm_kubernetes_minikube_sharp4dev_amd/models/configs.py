@@ -94,6 +94,23 @@ ENCODERS = {
 }
 
 
+# Cross-encoder rerankers (BertForSequenceClassification, one label): a table of their own, so
+# whatever enumerates ENCODERS (the embedding routes, /api/tags) lists embedders only.
+RERANKERS = {
+    "ms-marco-minilm-l6": EncoderConfig("ms-marco-minilm-l6", "bert", 6, 384, 12, 1536, 30522,
+                                        max_position=512, type_vocab_size=2, pooling="cls"),
+    # bert-tiny's dimensions; vocab = the built-in tokenizer's 32768
+    "rerank-tiny": EncoderConfig("rerank-tiny", "bert", 2, 128, 2, 256, 32768, max_position=512, pooling="cls"),
+}
+
+
+def reranker_config(name: str, **overrides) -> EncoderConfig:
+    cfg = dataclasses.replace(RERANKERS[name])
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
 def decoder_config(name: str, **overrides) -> DecoderConfig:
     cfg = dataclasses.replace(DECODERS[name])
     for k, v in overrides.items():

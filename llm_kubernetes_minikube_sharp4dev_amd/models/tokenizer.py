@@ -189,6 +189,26 @@ class Tokenizer:
             out.append([self.cls_id] + ids + [self.sep_id])
         return out
 
+    def encode_pairs(self, query: str, docs: list[str], max_len: int = 512) -> tuple[list[list[int]], list[list[int]]]:
+        """Cross-encoder pairs ``[CLS] q [SEP] d [SEP]`` -> (ids, type_ids), one list per document;
+        type 0 covers ``[CLS] q [SEP]``, type 1 covers ``d [SEP]``.
+
+        Truncation: the query is cut to at most ``(max_len - 3) // 2`` tokens, the document to
+        whatever then remains of ``max_len``; both ``[SEP]`` are always present.  (HuggingFace's
+        ``longest_first`` instead removes tokens one at a time from whichever side is longer, so
+        an over-long pair may be cut differently there.)  The query is tokenised once."""
+        if max_len < 3:
+            raise ValueError("encode_pairs needs max_len >= 3")
+        q = self.encode(query)[: (max_len - 3) // 2]
+        head = [self.cls_id] + q + [self.sep_id]
+        room = max_len - len(head) - 1
+        ids, types = [], []
+        for d in self.encode_batch(docs):
+            d = d[:room]
+            ids.append(head + d + [self.sep_id])
+            types.append([0] * len(head) + [1] * (len(d) + 1))
+        return ids, types
+
     def decode(self, ids: list[int], skip_special: bool = True) -> str:
         ids = [i for i in ids if 0 <= i < self.vocab_size]
         return self.tok.decode(ids, skip_special_tokens=skip_special)

@@ -22,7 +22,7 @@ __all__ = [
     "pool_normalize", "row_norms", "select_tokens", "repeat_penalty_", "sample", "linear", "linear_swiglu",
     "decode_splits", "rope_cos_sin", "argmax_key", "key_to_id", "tune_gemm", "tune_decode", "gemm", "linear_add_rmsnorm", "linear_rope_kv",
     "prefill_chain_ok", "linear_resid", "linear_qkv_fused", "linear_swiglu_scaled", "embed_rows", "scatter_ids",
-    "gather_rows", "token_logprobs",
+    "gather_rows", "token_logprobs", "rerank_head",
 ]
 
 rope_cos_sin = ref.rope_cos_sin
@@ -275,6 +275,15 @@ def pool_normalize(hidden, cu, mode: int, normalize: bool = True, out=None):
         out.copy_(y)
         return out
     return y
+
+
+def rerank_head(hidden, cu, pool_w, pool_b, cls_w, cls_b, activation: int = 0):
+    """Cross-encoder score head over packed hidden rows [T, H] (``cu`` [B+1]): per sequence the CLS
+    row -> ``pool_w`` [H, H] (+ ``pool_b``) -> tanh -> ``cls_w`` [H] / [1, H] (+ ``cls_b``) -> f32 [B];
+    ``activation`` 0: the logit, 1: its sigmoid.  An empty sequence scores the zero vector."""
+    if use_hip(hidden):
+        return lib().rerank_head(hidden, cu, pool_w, pool_b, cls_w, cls_b, int(activation))
+    return ref.rerank_head(hidden, cu, pool_w, pool_b, cls_w, cls_b, int(activation))
 
 
 def row_norms(x):

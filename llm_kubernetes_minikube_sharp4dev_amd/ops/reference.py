@@ -266,6 +266,27 @@ def pool_normalize(hidden, cu, mode, normalize):
     return torch.stack(outs) if outs else hidden.new_zeros((0, hidden.shape[1]), dtype=torch.float32)
 
 
+def rerank_head(hidden, cu, pool_w, pool_b, cls_w, cls_b, activation=0):
+    """fp32, in the kernel's operation order: x = first row of each sequence (zeros if it is empty);
+    a = pool_w x + pool_b; s = tanh(a) . cls_w + cls_b; out = sigmoid(s) if activation else s."""
+    cu = [int(v) for v in cu]
+    H = hidden.shape[1]
+    W = pool_w.float().cpu()
+    c = cls_w.float().cpu().reshape(-1)
+    outs = []
+    for b in range(len(cu) - 1):
+        x = hidden[cu[b]].float().cpu() if cu[b + 1] > cu[b] else torch.zeros(H)
+        a = (W * x[None, :]).sum(-1)
+        if pool_b is not None:
+            a = a + pool_b.float().cpu()
+        s = (torch.tanh(a) * c).sum()
+        if cls_b is not None:
+            s = s + cls_b.float().cpu().reshape(())
+        outs.append(1.0 / (1.0 + torch.exp(-s)) if activation else s)
+    out = torch.stack(outs) if outs else torch.zeros(0)
+    return out.to(torch.float32).to(hidden.device)
+
+
 def row_norms(x):
     return x.float().norm(dim=-1)
 

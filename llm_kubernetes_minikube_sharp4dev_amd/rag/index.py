@@ -55,6 +55,7 @@ class RagHit:                        # record RagHit(Id, Source, Text, double Sc
     source: str
     text: str
     score: float
+    rerank_score: Optional[float] = None  # set by RagIndex.query(..., reranker=...)
 
 
 def cosine_exact(a: np.ndarray, b: np.ndarray) -> float:
@@ -239,9 +240,26 @@ class RagIndex:
             out.append([(int(j), float(scores[j])) for j in order])
         return out
 
-    def query(self, query: str, top_k: int = 5) -> list[RagHit]:
+    def query(self, query: str, top_k: int = 5, reranker=None, candidates: int = 24) -> list[RagHit]:
+        """Top ``top_k`` hits by cosine.  With a ``reranker`` (``score(query, docs) -> floats``, see
+        :mod:`.reranker`): ``max(top_k, candidates)`` cosine hits are scored by it and the best
+        ``top_k`` come back in rerank order (ties by cosine rank); every hit keeps its cosine as
+        ``score`` and carries the reranker's as ``rerank_score``."""
         qv = self.embedder.embed([query])
-        return self.hits(self.search_vectors(qv, top_k)[0])
+        if reranker is None:
+            return self.hits(self.search_vectors(qv, top_k)[0])
+        hits = self.hits(self.search_vectors(qv, max(top_k, candidates))[0])
+        if not hits:
+            return hits
+        rs = [float(s) for s in reranker.score(query, [h.text for h in hits])]
+        if len(rs) != len(hits):
+            raise ValueError(f"reranker returned {len(rs)} scores for {len(hits)} documents")
+        order = sorted(range(len(hits)), key=lambda i: (-rs[i], i))[:top_k]
+        out = []
+        for i in order:
+            hits[i].rerank_score = rs[i]
+            out.append(hits[i])
+        return out
 
     def query_batch(self, queries: Sequence[str], top_k: int = 5) -> list[list[RagHit]]:
         qv = self.embedder.embed(list(queries))

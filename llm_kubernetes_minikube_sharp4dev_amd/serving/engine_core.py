@@ -10,10 +10,12 @@ with a compact binary protocol:
   frame  = u32 little-endian length + msgpack body
   client -> core  ["gen", rid, model, ids, sampling-dict, format] | ["abort", rid]
                   | ["embed", rid, model, texts] | ["load", rid, model]
+                  | ["rerank", rid, model, query, docs, activation]
   core -> client  ["tok", [[rid, [ids..], finished, reason, cached_prefix, error], ...], stats]
                     (an item of a request that asked for logprobs has a 7th element: one
                     [chosen logprob, [[id, logprob], ...]] entry per id of the item)
                   | ["emb", rid, f32 bytes, rows, dim] | ["load", rid, meta] | ["err", rid, msg]
+                  | ["rr", rid, f32 score bytes, n, pair tokens encoded]
 
 Every engine step's tokens for one connection leave as ONE frame (the engine thread appends
 them, a writer thread per connection drains and sends), so the core's Python work per step is
@@ -267,6 +269,9 @@ class EngineCore:
         elif op == "embed":
             _, rid, model, texts = msg
             self._pool.submit(self._embed, conn, rid, model, texts)
+        elif op == "rerank":  # (activation: 0 logits, 1 sigmoid; optional on the wire)
+            _, rid, model, query, docs = msg[:5]
+            self._pool.submit(self._rerank, conn, rid, model, query, docs, int(msg[5]) if len(msg) > 5 else 1)
         elif op == "load":
             _, rid, model = msg
             self._pool.submit(self._load, conn, rid, model)
@@ -287,13 +292,24 @@ class EngineCore:
         except Exception as e:  # noqa: BLE001 - reported to the client
             conn.post(["err", rid, f"{type(e).__name__}: {e}"])
 
+    def _rerank(self, conn, rid, model, query, docs, activation):
+        try:
+            import numpy as np
+
+            h = self.mgr.reranker(model)
+            s, ntok = h.engine.score_cpu(query, list(docs), activation, return_tokens=True)
+            s = np.ascontiguousarray(s, dtype=np.float32)
+            conn.post(["rr", rid, s.tobytes(), int(s.shape[0]), int(ntok)])
+        except Exception as e:  # noqa: BLE001 - reported to the client
+            conn.post(["err", rid, f"{type(e).__name__}: {e}"])
+
     def _load(self, conn, rid, model):
         try:
             kind, _ = self.mgr.resolve(model)
             if kind == "generate":
                 conn.post(["load", rid, {"kind": kind, **self._meta(self.mgr.generator(model))}])
             else:
-                h = self.mgr.embedder(model)
+                h = self.mgr.reranker(model) if kind == "rerank" else self.mgr.embedder(model)
                 conn.post(["load", rid, {"kind": kind, "name": h.name, "preset": h.preset, "load_s": h.load_s}])
         except Exception as e:  # noqa: BLE001
             conn.post(["err", rid, f"{type(e).__name__}: {e}"])

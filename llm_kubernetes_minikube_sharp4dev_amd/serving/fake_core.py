@@ -15,6 +15,19 @@ import numpy as np
 _HDR = struct.Struct("<I")
 
 
+def fake_rerank_logit(query: str, doc: str) -> float:
+    """The fake core's score of a pair: a deterministic function of the two texts (CRC-32 of
+    ``query NUL doc`` mapped onto [-4, 4)), so front-end tests know every score without a model."""
+    import zlib
+
+    return (zlib.crc32((query + "\0" + doc).encode("utf-8")) % 8192) / 1024.0 - 4.0
+
+
+def fake_rerank_scores(query: str, docs: list, activation: int = 0) -> np.ndarray:
+    s = np.array([fake_rerank_logit(query, d) for d in docs], dtype=np.float32)
+    return (1.0 / (1.0 + np.exp(-s.astype(np.float64)))).astype(np.float32) if activation else s
+
+
 class FakeCore:
     def __init__(self, path: str, tokens: int = 48, step_s: float = 0.002, dim: int = 768, vocab: int = 32000):
         self.path, self.tokens, self.step_s, self.dim, self.vocab = path, tokens, step_s, dim, vocab
@@ -75,12 +88,18 @@ class FakeCore:
                     if active.pop(rid, None) is not None:
                         self.aborted += 1
                 elif op == "load":
-                    send(["load", rid, {"kind": "generate" if "embed" not in msg[2] else "embed", "name": msg[2],
+                    kind = "rerank" if "rerank" in msg[2] else ("generate" if "embed" not in msg[2] else "embed")
+                    send(["load", rid, {"kind": kind, "name": msg[2],
                                         "preset": msg[2], "max_model_len": 8192, "eos_ids": [], "chat_style": "llama3",
                                         "load_s": 0.0, "vocab_size": self.vocab}])
                 elif op == "embed":
                     v = np.ones((len(msg[3]), self.dim), np.float32) / np.sqrt(self.dim)
                     send(["emb", rid, v.tobytes(), v.shape[0], v.shape[1]])
+                elif op == "rerank":  # (token count: one per whitespace word of each pair)
+                    q, docs = msg[3], list(msg[4])
+                    s = fake_rerank_scores(q, docs, int(msg[5]) if len(msg) > 5 else 1)
+                    ntok = sum(len(q.split()) + len(d.split()) + 3 for d in docs)
+                    send(["rr", rid, s.tobytes(), len(docs), ntok])
         except (asyncio.IncompleteReadError, ConnectionError):
             pass
         finally:

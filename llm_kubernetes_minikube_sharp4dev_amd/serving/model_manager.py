@@ -24,8 +24,9 @@ import torch
 from ..config import Config
 from ..engine.embed_engine import EmbeddingEngine
 from ..engine.llm_engine import AsyncLLMEngine, LLMEngine
-from ..models import build_decoder, build_encoder
-from ..models.configs import DECODERS, ENCODERS, param_count
+from ..engine.rerank_engine import RerankEngine
+from ..models import build_decoder, build_encoder, build_reranker
+from ..models.configs import DECODERS, ENCODERS, RERANKERS, param_count
 from ..models.tokenizer import load_tokenizer
 from ..utils.logging import get_logger
 
@@ -53,6 +54,15 @@ class EmbedderHandle:
     load_s: float = 0.0
 
 
+@dataclass
+class RerankerHandle:
+    name: str
+    preset: str
+    engine: RerankEngine
+    loaded_at: float = field(default_factory=time.time)
+    load_s: float = 0.0
+
+
 class ModelManager:
     def __init__(self, cfg: Optional[Config] = None, device: Optional[str] = None,
                  aliases: Optional[dict] = None, checkpoints: Optional[dict] = None,
@@ -66,6 +76,7 @@ class ModelManager:
         self.engine_overrides = dict(engine_overrides or {})
         self.generators: dict[str, GeneratorHandle] = {}
         self.embedders: dict[str, EmbedderHandle] = {}
+        self.rerankers: dict[str, RerankerHandle] = {}
         self.lock = threading.RLock()
 
     # ------------------------------------------------------------ resolution
@@ -74,15 +85,20 @@ class ModelManager:
         n = self.aliases.get(name, name)
         base = n.split(":latest")[0]
         gens, embs = self.cfg.models.generators, self.cfg.models.embedders
+        rers = getattr(self.cfg.models, "rerankers", {})
         for cand in (n, base):
             if cand in gens:
                 return "generate", gens[cand]
             if cand in embs:
                 return "embed", embs[cand]
+            if cand in rers:
+                return "rerank", rers[cand]
             if cand in DECODERS:
                 return "generate", cand
             if cand in ENCODERS:
                 return "embed", cand
+            if cand in RERANKERS:
+                return "rerank", cand
         raise KeyError(f"model '{name}' not found")
 
     def known_models(self) -> list[tuple[str, str, str]]:
@@ -204,6 +220,22 @@ class ModelManager:
             log.info("loaded embedder %s (%s) in %.1fs", name, preset, h.load_s)
             return h
 
+    def reranker(self, name: str) -> RerankerHandle:
+        with self.lock:
+            if name in self.rerankers:
+                return self.rerankers[name]
+            kind, preset = self.resolve(name)
+            if kind != "rerank":
+                raise KeyError(f"model '{name}' does not support rerank")
+            t0 = time.perf_counter()
+            ck = self.checkpoints.get(name) or self.checkpoints.get(preset)
+            model = build_reranker(preset, device=self.device, seed=self.cfg.engine.seed, checkpoint=ck, dtype=self._dtype())
+            eng = RerankEngine(model, load_tokenizer(ck), name=name)
+            h = RerankerHandle(name, preset, eng, load_s=time.perf_counter() - t0)
+            self.rerankers[name] = h
+            log.info("loaded reranker %s (%s) in %.1fs", name, preset, h.load_s)
+            return h
+
     def details(self, name: str) -> dict:
         kind, preset = self.resolve(name)
         if kind == "generate":
@@ -211,7 +243,7 @@ class ModelManager:
             n = param_count(c)
             fam = c.arch
         else:
-            c = ENCODERS[preset]
+            c = RERANKERS[preset] if kind == "rerank" else ENCODERS[preset]
             n = c.num_layers * 12 * c.hidden * c.hidden + c.vocab_size * c.hidden
             fam = "nomic-bert" if c.arch == "nomic_bert" else "bert"
         size = f"{n / 1e9:.1f}B" if n >= 1e9 else f"{n / 1e6:.0f}M"

@@ -13,6 +13,8 @@ Routes (Ollama REST API):
   POST /api/embeddings legacy single embedding; accepts ``prompt`` AND ``input`` (str or
                        [str]) so the first payload of ``Embedder.cs:14`` succeeds
   POST /api/embed      batched ``input`` -> ``embeddings``
+  POST /v1/rerank, /api/rerank  cross-encoder scores of (query, document) pairs, sorted
+                       (docs/rerank.md)
   GET  /api/tags, POST /api/show, GET /api/ps, GET /api/version, GET|HEAD /
   POST /api/pull (presets are local: reports success), DELETE /api/delete
   OpenAI compatibility: POST /v1/chat/completions, /v1/completions, /v1/embeddings,
@@ -95,6 +97,23 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
     async def _emb_handle(model: str):
         h = mgr.embedders.get(model)
         return h if h is not None else await asyncio.to_thread(mgr.embedder, model)
+
+    async def _rr_handle(model: str):
+        h = mgr.rerankers.get(model)
+        return h if h is not None else await asyncio.to_thread(mgr.reranker, model)
+
+    def key_err(e: KeyError, model):
+        """A model that is not known is a 404; a rerank model asked for another capability, or
+        another model asked to rerank, is a 400 (the request names a model that exists)."""
+        msg = str(e).strip("'\"")
+        if "does not support" in msg:
+            try:
+                rr = "does not support rerank" in msg or mgr.resolve(model)[0] == "rerank"
+            except (KeyError, TypeError, AttributeError):
+                rr = False
+            if rr:
+                return err(400, msg)
+        return err(404, msg)
 
     async def body_of(request: Request) -> dict:
         raw = await request.body()
@@ -452,7 +471,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         try:
             _, v = await _embed(model, [text])
         except KeyError as e:
-            return err(404, str(e).strip("'\""))
+            return key_err(e, model)
         return JSONResponse({"embedding": v[0]})
 
     @app.post("/api/embed")
@@ -471,10 +490,72 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         try:
             h, v = await _embed(model, texts)
         except KeyError as e:
-            return err(404, str(e).strip("'\""))
+            return key_err(e, model)
         n_tok = sum(len(x) for x in h.engine.tokenize(texts)) if texts else 0
         return JSONResponse({"model": model, "embeddings": v, "total_duration": time.perf_counter_ns() - t0,
                              "load_duration": 0, "prompt_eval_count": n_tok})
+
+    # ------------------------------------------------------------------ rerank (docs/rerank.md)
+    RERANK_MAX_DOCS = 1024
+
+    async def rerank(request: Request):
+        """Cross-encoder second stage: ``relevance_score`` = sigmoid of the pair's logit (applied by
+        the score-head kernel), results by score descending, ties by index ascending."""
+        try:
+            b = await body_of(request)
+        except ValueError as e:
+            return err(400, str(e))
+        model, query, docs = b.get("model"), b.get("query"), b.get("documents")
+        if not model or not isinstance(model, str):
+            return err(400, "model is required")
+        if not isinstance(query, str) or not query.strip():
+            return err(400, "query must be a non-empty string")
+        if not isinstance(docs, list):
+            return err(400, "documents must be a list of strings or {\"text\": string} objects")
+        texts = []
+        for i, d in enumerate(docs):
+            t = d.get("text") if isinstance(d, dict) else d
+            if not isinstance(t, str):
+                return err(400, f"documents[{i}] must be a string or an object with a string \"text\"")
+            texts.append(t)
+        if len(texts) > RERANK_MAX_DOCS:
+            return err(400, f"documents holds {len(texts)} entries; at most {RERANK_MAX_DOCS} are accepted")
+        top_n = b.get("top_n")
+        if top_n is not None and (isinstance(top_n, bool) or not isinstance(top_n, int) or top_n < 1):
+            return err(400, "top_n must be an integer >= 1")
+        with_docs = b.get("return_documents", False)
+        if not isinstance(with_docs, bool):
+            return err(400, "return_documents must be a boolean")
+        try:
+            if texts:
+                h = await _rr_handle(model)
+            else:  # nothing to score: the model is only resolved, the device is not touched
+                if mgr.resolve(model)[0] != "rerank":
+                    raise KeyError(f"model '{model}' does not support rerank")
+        except KeyError as e:
+            return key_err(e, model)
+        except TypeError:
+            return err(404, f"model '{model}' not found")
+        if texts:
+            t0 = time.perf_counter()
+            scores, ntok = await asyncio.to_thread(h.engine.score_cpu, query, texts, 1, True)
+            tracing.record("server", "rerank_request", time.perf_counter() - t0, n=len(texts))
+            scores = [float(x) for x in scores]
+        else:
+            scores, ntok = [], 0
+        order = sorted(range(len(texts)), key=lambda i: (-scores[i], i))
+        if top_n is not None:
+            order = order[:top_n]
+        results = []
+        for i in order:
+            r = {"index": i, "relevance_score": scores[i]}
+            if with_docs:
+                r["document"] = {"text": texts[i]}
+            results.append(r)
+        return JSONResponse({"model": model, "results": results, "usage": {"total_tokens": int(ntok)}})
+
+    app.post("/v1/rerank")(rerank)
+    app.post("/api/rerank")(rerank)
 
     # ------------------------------------------------------------------ model admin
     def _tag(name, kind, preset):
@@ -486,7 +567,8 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
 
     @app.get("/api/tags")
     async def tags():
-        return {"models": [_tag(n, k, p) for n, k, p in mgr.known_models()]}
+        loaded = [(n, "rerank", h.preset) for n, h in list(mgr.rerankers.items())]  # listed once loaded
+        return {"models": [_tag(n, k, p) for n, k, p in mgr.known_models() + loaded]}
 
     @app.post("/api/show")
     async def show(request: Request):
@@ -496,7 +578,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
             d = mgr.details(name)
         except (KeyError, TypeError):
             return err(404, f"model '{name}' not found")
-        caps = ["completion"] if d["kind"] == "generate" else ["embedding"]
+        caps = {"generate": ["completion"], "rerank": ["rerank"]}.get(d["kind"], ["embedding"])
         return {"modelfile": f"FROM {d['preset']}\n", "parameters": "", "template": "{{ .Prompt }}",
                 "details": {k: d[k] for k in ("format", "family", "families", "parameter_size", "quantization_level")},
                 "model_info": {"general.architecture": d["family"], "general.parameter_count": d["params"]},
@@ -534,7 +616,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
     @app.get("/api/ps")
     async def ps():
         out = []
-        for n, h in list(mgr.generators.items()) + list(mgr.embedders.items()):
+        for n, h in list(mgr.generators.items()) + list(mgr.embedders.items()) + list(mgr.rerankers.items()):
             out.append({"name": n, "model": n, "size": 0, "digest": "", "details": {}, "expires_at": "0001-01-01T00:00:00Z",
                         "size_vram": 0})
         return {"models": out}
@@ -555,6 +637,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         name = b.get("model") or b.get("name")
         mgr.generators.pop(name, None)
         mgr.embedders.pop(name, None)
+        mgr.rerankers.pop(name, None)
         return Response(status_code=200)
 
     @app.get("/api/version")

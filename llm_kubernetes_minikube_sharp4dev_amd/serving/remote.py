@@ -310,6 +310,51 @@ class RemoteEmbedderHandle:
     load_s: float = 0.0
 
 
+class _RemoteRerank:
+    """Front-end handle of a reranker that lives in the engine cores."""
+
+    def __init__(self, pool: CorePool, model: str):
+        self.pool, self.model = pool, model
+
+    def score_cpu(self, query: str, docs: list, activation: int = 0, return_tokens: bool = False):
+        """Blocking, like ``_RemoteEmbed.embed_cpu`` (never call it on the core connection's loop)."""
+        if not docs:
+            s, ntok = np.zeros((0,), np.float32), 0
+        else:
+            c = self.pool.pick()
+            try:
+                running = asyncio.get_running_loop()
+            except RuntimeError:
+                running = None
+            if running is not None and running is c.loop:
+                raise RuntimeError("_RemoteRerank.score_cpu called on the core connection's event loop; "
+                                   "use score_async")
+            fut = asyncio.run_coroutine_threadsafe(
+                c.request("rerank", self.model, query, list(docs), int(activation)), c.loop)
+            s, ntok = self._decode(fut.result())
+        return (s, ntok) if return_tokens else s
+
+    async def score_async(self, query: str, docs: list, activation: int = 0):
+        """Non-blocking form for callers on the core connection's loop -> (scores, tokens)."""
+        if not docs:
+            return np.zeros((0,), np.float32), 0
+        return self._decode(await self.pool.pick().request("rerank", self.model, query, list(docs), int(activation)))
+
+    @staticmethod
+    def _decode(msg):
+        _, _, data, n, ntok = msg
+        return np.frombuffer(data, dtype=np.float32)[:n].copy(), int(ntok)
+
+
+@dataclass
+class RemoteRerankerHandle:
+    name: str
+    preset: str
+    engine: _RemoteRerank
+    loaded_at: float = field(default_factory=time.time)
+    load_s: float = 0.0
+
+
 class RemoteModelManager(ModelManager):
     """ModelManager whose models live in engine-core processes.  Never touches the GPU."""
 
@@ -324,6 +369,7 @@ class RemoteModelManager(ModelManager):
         self.engine_overrides = {}
         self.generators: dict = {}
         self.embedders: dict = {}
+        self.rerankers: dict = {}
         self.lock = threading.RLock()
         self.pool = CorePool(core_paths)
 
@@ -368,6 +414,18 @@ class RemoteModelManager(ModelManager):
             self.embedders[name] = h
             return h
 
+    def reranker(self, name: str):
+        with self.lock:
+            if name in self.rerankers:
+                return self.rerankers[name]
+            kind, preset = self.resolve(name)
+            if kind != "rerank":
+                raise KeyError(f"model '{name}' does not support rerank")
+            meta = self._load_remote(name)
+            h = RemoteRerankerHandle(name, preset, _RemoteRerank(self.pool, name), load_s=meta["load_s"])
+            self.rerankers[name] = h
+            return h
+
     def shutdown(self):
         pass
 
@@ -385,7 +443,7 @@ def create_frontend_app(core_paths: list[str], cfg: Optional[Config] = None, ali
         await mgr.pool.connect()
         for m in preload or []:
             kind, _ = mgr.resolve(m)
-            await asyncio.to_thread(mgr.generator if kind == "generate" else mgr.embedder, m)
+            await asyncio.to_thread({"generate": mgr.generator, "rerank": mgr.reranker}.get(kind, mgr.embedder), m)
 
     return app
 
