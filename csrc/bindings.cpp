@@ -696,6 +696,56 @@ std::vector<at::Tensor> knn_merge(const at::Tensor& cand_s, const at::Tensor& ca
   return {out_s, out_i};
 }
 
+// BM25 top-K over a CSR-by-term inverted index (csrc/bm25.hip + the kNN merge): -> (scores f32
+// [nq, K], ids int32 [nq, K]), (score desc, id asc), documents with score > 0 only, (-inf, -1) pads.
+// q_ptr may live on the host or the device; its host copy is checked here (it bounds every read of
+// q_term / q_w), so a malformed query never reaches the kernel.
+std::vector<at::Tensor> bm25_topk(const at::Tensor& term_ptr, const at::Tensor& post_doc, const at::Tensor& post_tf,
+                                  const at::Tensor& kn, const at::Tensor& q_ptr, const at::Tensor& q_term,
+                                  const at::Tensor& q_w, int64_t K) {
+  CHECK_CUDA(term_ptr); CHECK_CONTIG(term_ptr); TORCH_CHECK(term_ptr.scalar_type() == at::kLong, "term_ptr must be int64");
+  CHECK_CUDA(post_doc); CHECK_I32(post_doc); CHECK_CONTIG(post_doc);
+  CHECK_CUDA(post_tf); CHECK_CONTIG(post_tf); TORCH_CHECK(post_tf.scalar_type() == at::kByte, "post_tf must be uint8");
+  CHECK_CUDA(kn); CHECK_F32(kn); CHECK_CONTIG(kn);
+  CHECK_I32(q_ptr); CHECK_CONTIG(q_ptr);
+  CHECK_CUDA(q_term); CHECK_I32(q_term); CHECK_CONTIG(q_term); CHECK_CUDA(q_w); CHECK_F32(q_w); CHECK_CONTIG(q_w);
+  TORCH_CHECK(term_ptr.dim() == 1 && term_ptr.numel() >= 1, "term_ptr must be [V+1]");
+  TORCH_CHECK(post_doc.dim() == 1 && post_tf.dim() == 1 && post_doc.numel() == post_tf.numel(), "post_doc / post_tf must be [nnz]");
+  TORCH_CHECK(kn.dim() == 1, "kn must be [N]");
+  TORCH_CHECK(q_ptr.dim() == 1 && q_ptr.numel() >= 1, "q_ptr must be [nq+1]");
+  TORCH_CHECK(q_term.dim() == 1 && q_w.dim() == 1 && q_term.numel() == q_w.numel(), "q_term / q_w must be [nt]");
+  const long V = term_ptr.numel() - 1, nnz = post_doc.numel(), N = kn.numel(), nt = q_term.numel();
+  const int nq = (int)(q_ptr.numel() - 1);
+  const at::Tensor qh = q_ptr.cpu();
+  const int* qp = qh.data_ptr<int>();
+  int max_terms = 0;
+  TORCH_CHECK(qp[0] == 0 && qp[nq] == nt, "bm25_topk: q_ptr must run from 0 to the number of query terms (", nt,
+              "), got ", qp[0], " .. ", qp[nq]);
+  for (int i = 0; i < nq; ++i) {
+    TORCH_CHECK(qp[i + 1] >= qp[i], "bm25_topk: q_ptr must be non-decreasing");
+    max_terms = std::max(max_terms, qp[i + 1] - qp[i]);
+  }
+  CHECK_RC(lk_bm25_supported(N, nq, max_terms, (int)std::min<int64_t>(std::max<int64_t>(K, -1), 1 << 20)), "bm25_topk");
+  auto fo = kn.options().dtype(at::kFloat);
+  auto io = kn.options().dtype(at::kInt);
+  if (N == 0 || nq == 0) return {at::full({nq, (long)K}, -INFINITY, fo), at::full({nq, (long)K}, -1, io)};
+  const at::Tensor qd = q_ptr.is_cuda() ? q_ptr : q_ptr.to(kn.device());
+  const int nc = lk_bm25_chunks(N);
+  at::Tensor ps = at::empty({nq, nc, (long)K}, fo);
+  at::Tensor pi = at::empty({nq, nc, (long)K}, io);
+  at::Tensor out_s = at::empty({nq, (long)K}, fo);
+  at::Tensor out_i = at::empty({nq, (long)K}, io);
+  int rc = lk_bm25_partial(reinterpret_cast<const long*>(term_ptr.data_ptr<int64_t>()), V, ip(post_doc),
+                           post_tf.data_ptr<uint8_t>(), nnz, kn.data_ptr<float>(), N, ip(qd), ip(q_term),
+                           q_w.data_ptr<float>(), nq, max_terms, (int)K, ps.data_ptr<float>(), pi.data_ptr<int>(),
+                           cur_stream());
+  CHECK_RC(rc, "bm25_topk");
+  rc = lk_knn_merge(ps.data_ptr<float>(), pi.data_ptr<int>(), nq, nc * (int)K, (int)K, out_s.data_ptr<float>(),
+                    out_i.data_ptr<int>(), cur_stream());
+  CHECK_RC(rc, "bm25 merge");
+  return {out_s, out_i};
+}
+
 // out: optional destination rows [B, H] (f32 or bf16, unit last stride, 16-byte rows), e.g. a
 // slice of the caller's embedding matrix; default a new f32 [B, H]
 at::Tensor pool_normalize(const at::Tensor& hidden, const at::Tensor& cu, int64_t mode, bool normalize,
@@ -1126,6 +1176,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_topk", &knn_topk, "", py::arg("corpus"), py::arg("cnorm"), py::arg("queries"), py::arg("qnorm"),
         py::arg("K"), py::arg("force_fused") = false);
   m.def("knn_merge", &knn_merge);
+  m.def("bm25_topk", &bm25_topk, "", py::arg("term_ptr"), py::arg("post_doc"), py::arg("post_tf"), py::arg("kn"),
+        py::arg("q_ptr"), py::arg("q_term"), py::arg("q_w"), py::arg("K"));
+  m.attr("BM25_CHUNK") = kLkBm25Chunk;
+  m.attr("BM25_MAX_TERMS") = kLkBm25MaxTerms;
   m.def("pool_normalize", &pool_normalize, "", py::arg("hidden"), py::arg("cu"), py::arg("mode"), py::arg("normalize"),
         py::arg("out") = py::none());
   m.def("rerank_head", &rerank_head, "", py::arg("hidden"), py::arg("cu"), py::arg("pool_w"), py::arg("pool_b"),

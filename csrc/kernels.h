@@ -175,6 +175,22 @@ int lk_knn_score_topk(const float* scores, long ld, const float* cnorm, const fl
 int lk_knn_merge(const float* cand_s, const int* cand_i, int nq, int ncand, int K, float* out_s,
                  int* out_i, hipStream_t st);
 
+// bm25.hip
+// BM25 posting scan + per-chunk top-k over a CSR-by-term inverted index: term_ptr int64 [V+1],
+// post_doc int32 [nnz] (strictly ascending inside a term), post_tf uint8 [nnz], kn f32 [N];
+// queries as CSR too: q_ptr int32 [nq+1], q_term int32 / q_w f32 [q_ptr[nq]], terms ascending.
+// part_s / part_i [nq, lk_bm25_chunks(N), K]: each chunk's best K documents with score > 0 by
+// (score desc, id asc), padded with (-inf, -1); lk_knn_merge finishes.  max_terms: the longest
+// query's term count (from the host copy of q_ptr).  Refused: K outside 1..64 (-1), max_terms >
+// kLkBm25MaxTerms (-2), N >= 2^31 (-3), nq > 65535 (-4).
+constexpr int kLkBm25Chunk = 4096;   // document ids per workgroup
+constexpr int kLkBm25MaxTerms = 64;  // unique terms per query
+int lk_bm25_chunks(long N);
+int lk_bm25_supported(long N, int nq, int max_terms, int K);
+int lk_bm25_partial(const long* term_ptr, long V, const int* post_doc, const unsigned char* post_tf, long nnz,
+                    const float* kn, long N, const int* q_ptr, const int* q_term, const float* q_w, int nq,
+                    int max_terms, int K, float* part_s, int* part_i, hipStream_t st);
+
 // pooling.hip
 int lk_pool_normalize(const bf16_t* hidden, long hs, const int* cu, int B, int H, int mode,
                       int normalize, void* out, long os, int out_bf16, hipStream_t st);

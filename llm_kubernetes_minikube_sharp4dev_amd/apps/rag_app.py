@@ -3,7 +3,8 @@ and JSON contracts:
 
   GET  /health       -> {"status":"ok"}                                  (C2, :55)
   POST /rag/search   pure retrieval, topK default 5 clamp [1,10], best-score
-                     0.20 floor, 260-char previews                        (C3, :62-100)
+                     0.20 floor, 260-char previews                        (C3, :62-100);
+                     optional "mode": dense | lexical | hybrid (docs/hybrid_search.md)
   POST /agent_rag    retrieve top-6 -> citations -> LLM tool call -> gated k8s
                      action -> {result, citations, note}                  (C4, :106-316)
 
@@ -25,7 +26,7 @@ from ..agent.json_extract import extract_json_object
 from ..agent.policy import select_citations
 from ..agent.prompts import RAG_AGENT_SYSTEM, json_prompt, rag_agent_input
 from ..agent.tools import dispatch_rag_tool
-from ..config import Config
+from ..config import SEARCH_MODES, Config
 from ..rag.chunking import is_blank, u16len, u16slice
 from ..utils import metrics as M
 from ..utils.logging import get_logger
@@ -49,6 +50,8 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
     if r.rerank_model and reranker is None:
         raise ValueError(f"rag.rerank_model is '{r.rerank_model}' but no reranker was given to the RAG app")
     app.state.reranker = reranker if r.rerank_model else None
+    if r.search_mode not in SEARCH_MODES:
+        raise ValueError(f"rag.search_mode must be one of {', '.join(SEARCH_MODES)} (got '{r.search_mode}')")
     tracer = Tracer("rag_app")
     app.state.tracer = tracer
     if build_index and index is not None and len(index) == 0:
@@ -56,6 +59,10 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
             index.build_incremental(r.knowledge_dir, r.cache_dir, r.chunk_size, r.chunk_overlap)
         else:
             index.build_from_folder(r.knowledge_dir, r.chunk_size, r.chunk_overlap)
+    if hasattr(index, "configure_lexical"):
+        index.configure_lexical(r.hybrid_candidates, r.rrf_k, r.bm25_k1, r.bm25_b)
+        if r.search_mode != "dense" and len(index):
+            index.lexical()  # at start-up, not on the first query
     if cfg.server.https_redirection:
         add_https_redirection(app, cfg.server.rag_https_port)
 
@@ -86,9 +93,12 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
     async def health():
         return NetJSONResponse({"status": "ok"})
 
-    def _rr(h) -> dict:  # (absent without a reranker: the response is unchanged)
+    def _rr(h) -> dict:  # (absent in mode 'dense' / without a reranker: the response is unchanged)
+        out = {}
+        if getattr(h, "fused_score", None) is not None:
+            out = {"lexicalScore": h.lexical_score, "fusedScore": h.fused_score}
         rs = getattr(h, "rerank_score", None)
-        return {} if rs is None else {"rerankScore": rs}
+        return out if rs is None else {**out, "rerankScore": rs}
 
     @app.post("/rag/search")
     async def rag_search(request: Request):
@@ -99,11 +109,24 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
             top_k = member(body, "topK", "int")
         except BindError:
             return Response(status_code=400)
+        mode = None
+        for key, val in body.items():  # case-insensitive, like member()
+            if key.lower() == "mode":
+                mode = val
+        if mode is None:
+            mode = r.search_mode
+        if not isinstance(mode, str) or mode not in SEARCH_MODES:
+            return NetJSONResponse({"error": f"mode must be one of {', '.join(SEARCH_MODES)}"}, status_code=400)
         if is_blank(query):
             return NetJSONResponse({"error": "Query vuota"}, status_code=400)
         k = r.search_default_topk if top_k is None else min(max(top_k, r.search_topk_min), r.search_topk_max)
         with tracer.span("rag.search", k=k):
-            if app.state.reranker is None:
+            if mode != "dense":  # opt-in first stage: BM25 alone, or fused with the cosine list
+                try:
+                    hits = await asyncio.to_thread(index.query, query, k, app.state.reranker, r.rerank_candidates, mode)
+                except ValueError as e:  # a sharded corpus serves 'dense' only
+                    return NetJSONResponse({"error": f"mode: {e}"}, status_code=400)
+            elif app.state.reranker is None:
                 hits = await asyncio.to_thread(index.query, query, k)
             else:  # opt-in second stage: the best k of the cosine candidates, in rerank order
                 hits = await asyncio.to_thread(index.query, query, k, app.state.reranker, r.rerank_candidates)

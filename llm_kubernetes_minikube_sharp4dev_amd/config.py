@@ -17,6 +17,9 @@ from pathlib import Path
 from typing import Any, Optional
 
 
+SEARCH_MODES = ("dense", "lexical", "hybrid")  # rag.search_mode / the "mode" of POST /rag/search
+
+
 @dataclass
 class RagConfig:
     """Retrieval constants (reference RAG service)."""
@@ -46,6 +49,11 @@ class RagConfig:
     cache_dir: str = ""                                # persisted embeddings (checkpoint/resume)
     rerank_model: Optional[str] = None                 # /rag/search second stage (off unless set)
     rerank_candidates: int = 24                        # cosine hits handed to the reranker
+    search_mode: str = "dense"                         # /rag/search first stage: dense | lexical | hybrid
+    hybrid_candidates: int = 24                        # hits taken from each list before the fusion
+    rrf_k: int = 60                                    # reciprocal-rank fusion: 1 / (rrf_k + rank)
+    bm25_k1: float = 1.2
+    bm25_b: float = 0.75
 
 
 @dataclass

@@ -22,7 +22,7 @@ __all__ = [
     "pool_normalize", "row_norms", "select_tokens", "repeat_penalty_", "sample", "linear", "linear_swiglu",
     "decode_splits", "rope_cos_sin", "argmax_key", "key_to_id", "tune_gemm", "tune_decode", "gemm", "linear_add_rmsnorm", "linear_rope_kv",
     "prefill_chain_ok", "linear_resid", "linear_qkv_fused", "linear_swiglu_scaled", "embed_rows", "scatter_ids",
-    "gather_rows", "token_logprobs", "rerank_head",
+    "gather_rows", "token_logprobs", "rerank_head", "bm25_topk",
 ]
 
 rope_cos_sin = ref.rope_cos_sin
@@ -263,6 +263,20 @@ def knn_merge(cand_s, cand_i, K: int):
             out_s[r, j] = s
             out_i[r, j] = i
     return out_s, out_i
+
+
+def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K: int):
+    """BM25 top-K over a CSR-by-term inverted index (docs/hybrid_search.md): ``score(d) = sum_t
+    w_t * tf / (tf + kn[d])`` over the query's terms (ascending ids) that have a posting for ``d``,
+    accumulated in fp32 -> (scores f32 [nq, K], ids int32 [nq, K]) ordered by (score desc, id
+    asc); only documents with score > 0 are hits, the rest of a row is (-inf, -1).  ``term_ptr``
+    int64 [V+1], ``post_doc`` int32 [nnz] (strictly ascending inside a term), ``post_tf`` uint8 [nnz],
+    ``kn`` f32 [N]; ``q_ptr`` int32 [nq+1] (host or device), ``q_term`` int32 / ``q_w`` f32 [nt].
+    K outside 1..64, a query of more than 64 terms or a ``q_ptr`` that does not match raise."""
+    if use_hip(post_doc):
+        s, i = lib().bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, int(K))
+        return s, i
+    return ref.bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K)
 
 
 def pool_normalize(hidden, cu, mode: int, normalize: bool = True, out=None):

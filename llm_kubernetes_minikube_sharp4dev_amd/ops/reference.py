@@ -254,6 +254,52 @@ def knn_topk(corpus, cnorm, queries, qnorm, K):
     return stable_topk(sc, K)
 
 
+BM25_CHUNK = 4096     # csrc/kernels.h kLkBm25Chunk (the reference has no chunks; exported for the tests)
+BM25_MAX_TERMS = 64   # csrc/kernels.h kLkBm25MaxTerms
+
+
+def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K):
+    """fp32, in the kernel's operation order: per query, over its terms as given (ascending ids),
+    ``score[d] += w_t * (tf / (tf + kn[d]))`` for every posting (d, tf) of the term -- the quotient,
+    the product and the add each rounded to f32 -- then the documents with score > 0 ordered by
+    (score desc, id asc); (-inf, -1) pads.  The index is CSR by term: ``term_ptr`` int64 [V+1],
+    ``post_doc`` int32 [nnz] strictly ascending inside a term, ``post_tf`` uint8 [nnz], ``kn`` f32
+    [N]; the queries ``q_ptr`` int32 [nq+1], ``q_term`` int32 / ``q_w`` f32 [nt]."""
+    import numpy as np
+
+    K = int(K)
+    tp = term_ptr.cpu().numpy().astype(np.int64)
+    pd = post_doc.cpu().numpy().astype(np.int64)
+    tf = post_tf.cpu().numpy().astype(np.float32)
+    knv = kn.cpu().numpy().astype(np.float32)
+    qp = q_ptr.cpu().numpy().astype(np.int64)
+    qt = q_term.cpu().numpy().astype(np.int64)
+    qw = q_w.cpu().numpy().astype(np.float32)
+    N, nq, V = len(knv), len(qp) - 1, len(tp) - 1
+    if len(qt) != len(qw) or nq < 0 or qp[0] != 0 or qp[-1] != len(qt) or np.any(np.diff(qp) < 0):
+        raise ValueError(f"bm25_topk: q_ptr must run from 0 to the number of query terms ({len(qt)})")
+    if not 1 <= K <= 64:
+        raise ValueError(f"bm25_topk: K must be in [1, 64] (got {K})")
+    if nq and int(np.diff(qp).max()) > BM25_MAX_TERMS:
+        raise ValueError(f"bm25_topk: a query has more than {BM25_MAX_TERMS} terms")
+    out_s = np.full((nq, K), -np.inf, dtype=np.float32)
+    out_i = np.full((nq, K), -1, dtype=np.int32)
+    for q in range(nq):
+        sc = np.zeros(N, dtype=np.float32)
+        for j in range(qp[q], qp[q + 1]):
+            t = qt[j]
+            if not 0 <= t < V:
+                continue
+            d = pd[tp[t]:tp[t + 1]]
+            f = tf[tp[t]:tp[t + 1]]
+            sc[d] = sc[d] + qw[j] * (f / (f + knv[d]))  # a document appears once per term: no lost update
+        hit = np.flatnonzero(sc > 0)
+        order = hit[np.lexsort((hit, -sc[hit]))][:K]
+        out_s[q, :len(order)] = sc[order]
+        out_i[q, :len(order)] = order
+    return torch.from_numpy(out_s), torch.from_numpy(out_i)
+
+
 def pool_normalize(hidden, cu, mode, normalize):
     cu = [int(x) for x in cu]
     outs = []

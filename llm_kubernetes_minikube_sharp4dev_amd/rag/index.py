@@ -24,6 +24,7 @@ from __future__ import annotations
 import hashlib
 import json
 import os
+import threading
 import time
 from dataclasses import dataclass
 from pathlib import Path
@@ -33,13 +34,16 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..config import SEARCH_MODES
 from ..utils import metrics as M
 from ..utils.logging import get_logger
+from ..utils.tracing import Tracer
 from .chunking import chunk_document, chunk_sliding, is_blank, sanitize, split_by_markdown_headers
 
 log = get_logger("rag")
 
 EXTENSIONS = (".md", ".txt", ".yaml", ".yml")
+_tracer = Tracer("rag_index")
 
 
 @dataclass
@@ -56,6 +60,8 @@ class RagHit:                        # record RagHit(Id, Source, Text, double Sc
     text: str
     score: float
     rerank_score: Optional[float] = None  # set by RagIndex.query(..., reranker=...)
+    lexical_score: Optional[float] = None  # BM25, modes 'lexical' / 'hybrid'; None: not in the lexical list
+    fused_score: Optional[float] = None    # reciprocal-rank fusion score, modes 'lexical' / 'hybrid'
 
 
 def cosine_exact(a: np.ndarray, b: np.ndarray) -> float:
@@ -68,6 +74,16 @@ def cosine_exact(a: np.ndarray, b: np.ndarray) -> float:
     na = float(np.sum((a * a).astype(np.float64)))
     nb = float(np.sum((b * b).astype(np.float64)))
     return dot / (np.sqrt(na) * np.sqrt(nb) + 1e-9)
+
+
+def rrf_fuse(lists: Sequence[Sequence[int]], rrf_k: int = 60) -> dict[int, float]:
+    """Reciprocal-rank fusion of ranked id lists: fused(d) = sum over the lists holding d of
+    1 / (rrf_k + rank), rank 1-based.  Order by (-fused, id)."""
+    fused: dict[int, float] = {}
+    for ranked in lists:
+        for rank, d in enumerate(ranked, 1):
+            fused[d] = fused.get(d, 0.0) + 1.0 / (rrf_k + rank)
+    return fused
 
 
 def enumerate_files(folder: str) -> list[str]:
@@ -92,6 +108,11 @@ class RagIndex:
         self._mat: Optional[np.ndarray] = None
         self._gpu = None                       # (corpus bf16, norms f32) on device
         self.file_hashes: dict[str, str] = {}
+        # lexical side of hybrid search (rag/lexical.py): built lazily from the chunk texts, never
+        # persisted; RagConfig's hybrid_candidates / rrf_k / bm25_k1 / bm25_b (configure_lexical)
+        self._lex = None
+        self._lex_lock = threading.Lock()
+        self.hybrid_candidates, self.rrf_k, self.bm25_k1, self.bm25_b = 24, 60, 1.2, 0.75
 
     # ------------------------------------------------------------ ingestion
     def __len__(self):
@@ -103,6 +124,7 @@ class RagIndex:
             self._emb.append(np.asarray(e, dtype=np.float32))
         self._mat = None
         self._gpu = None
+        self._lex = None
 
     def build_from_folder(self, folder: str, chunk_size: int = 800, overlap: int = 120,
                           batch_chunks: int = 4096) -> int:
@@ -240,15 +262,103 @@ class RagIndex:
             out.append([(int(j), float(scores[j])) for j in order])
         return out
 
-    def query(self, query: str, top_k: int = 5, reranker=None, candidates: int = 24) -> list[RagHit]:
+    # ------------------------------------------------------------ lexical / hybrid
+    def configure_lexical(self, hybrid_candidates: int = 24, rrf_k: int = 60, bm25_k1: float = 1.2,
+                          bm25_b: float = 0.75):
+        """RagConfig's hybrid-search settings; a changed k1 / b drops a built lexical index."""
+        if (bm25_k1, bm25_b) != (self.bm25_k1, self.bm25_b):
+            self._lex = None
+        self.hybrid_candidates, self.rrf_k, self.bm25_k1, self.bm25_b = hybrid_candidates, rrf_k, bm25_k1, bm25_b
+
+    def lexical(self):
+        """The BM25 index over the chunk texts (:class:`.lexical.LexicalIndex`), built on first use
+        under a lock and dropped by :meth:`add` / :meth:`load`: on the device when the vector
+        search runs there, else on the host (the fp32 reference of ``ops.bm25_topk``)."""
+        lex = self._lex
+        if lex is None:
+            from .lexical import LexicalIndex
+
+            with self._lex_lock:
+                lex = self._lex
+                if lex is None:
+                    dev = self.device if self.device.type == "cuda" and self._use_gpu() else torch.device("cpu")
+                    lex = LexicalIndex([c.text for c in self.chunks], self.bm25_k1, self.bm25_b, dev)
+                    self._lex = lex
+        return lex
+
+    def cosines(self, qv: np.ndarray, idx: Sequence[int]) -> list[float]:
+        """Cosine of one query vector against the corpus rows ``idx`` (the hits that only the lexical
+        list found): the arithmetic of the backend's scan -- float64 sums of f32 products on the
+        exact backend, the bf16 rows with an fp32 dot on the GPU backend."""
+        if not len(idx):
+            return []
+        if self._use_gpu():
+            corpus, norms = self.gpu_tensors()
+            if qv.shape[-1] != corpus.shape[1]:
+                raise ValueError(f"query width {qv.shape[-1]} != corpus width {corpus.shape[1]}")
+            ix = torch.as_tensor(list(idx), dtype=torch.long, device=corpus.device)
+            q = torch.as_tensor(qv, dtype=torch.float32).to(torch.bfloat16).to(corpus.device).float().reshape(-1)
+            dot = corpus[ix].float() @ q
+            return (dot / (q.norm() * norms[ix] + 1e-9)).tolist()
+        mat = self.matrix()[list(idx)]
+        qv = np.asarray(qv, dtype=np.float32).reshape(-1)
+        if qv.shape[-1] != mat.shape[1]:
+            return [-1.0] * len(idx)
+        prod = (mat * qv[None, :]).astype(np.float64).sum(1)
+        na = float(np.sum((qv * qv).astype(np.float64)))
+        nb = (mat * mat).astype(np.float64).sum(1)
+        return (prod / (np.sqrt(na) * np.sqrt(nb) + 1e-9)).tolist()
+
+    def _query_fused(self, query: str, k: int, take: int, mode: str) -> list[RagHit]:
+        """The best ``take`` chunks of the lexical order ('lexical') or of the reciprocal-rank fusion
+        of the lexical and the cosine list ('hybrid'): fused(d) = sum over the lists holding d of
+        1 / (rrf_k + rank), rank 1-based, sorted by fused descending, ties by lower chunk index."""
+        if getattr(self, "_sharded", None) is not None:
+            raise ValueError(f"mode '{mode}' is not supported with a sharded (tensor-parallel) corpus: use 'dense'")
+        if not self.chunks:
+            return []
+        cn = min(64, max(k, int(self.hybrid_candidates)))
+        qv = self.embedder.embed([query])
+        with _tracer.span("rag.lexical", mode=mode, candidates=cn):
+            lex = self.lexical().search([query], cn)[0]
+        bm25 = dict(lex)
+        cos: dict[int, float] = {}
+        lists = [[d for d, _ in lex]]
+        if mode == "hybrid":
+            dense = self.search_vectors(qv, cn)[0]
+            cos = dict(dense)
+            lists.append([d for d, _ in dense])
+        fused = rrf_fuse(lists, self.rrf_k)
+        order = sorted(fused, key=lambda d: (-fused[d], d))[:take]
+        missing = [d for d in order if d not in cos]
+        cos.update(zip(missing, self.cosines(np.asarray(qv)[0], missing)))
+        return [RagHit(self.chunks[d].id, self.chunks[d].source, self.chunks[d].text, float(cos[d]),
+                       lexical_score=bm25.get(d), fused_score=fused[d]) for d in order]
+
+    def query(self, query: str, top_k: int = 5, reranker=None, candidates: int = 24, mode: str = "dense") -> list[RagHit]:
         """Top ``top_k`` hits by cosine.  With a ``reranker`` (``score(query, docs) -> floats``, see
         :mod:`.reranker`): ``max(top_k, candidates)`` cosine hits are scored by it and the best
         ``top_k`` come back in rerank order (ties by cosine rank); every hit keeps its cosine as
-        ``score`` and carries the reranker's as ``rerank_score``."""
-        qv = self.embedder.embed([query])
-        if reranker is None:
-            return self.hits(self.search_vectors(qv, top_k)[0])
-        hits = self.hits(self.search_vectors(qv, max(top_k, candidates))[0])
+        ``score`` and carries the reranker's as ``rerank_score``.
+
+        ``mode`` 'lexical' orders by BM25 and 'hybrid' by the reciprocal-rank fusion of the BM25 and
+        the cosine list, ``min(64, max(top_k, hybrid_candidates))`` hits from each
+        (docs/hybrid_search.md); the hits carry ``lexical_score`` and ``fused_score``, ``score`` stays
+        the cosine, and a reranker scores the best ``max(top_k, candidates)`` of that order.  'dense'
+        (the default) is the cosine scan alone."""
+        if mode not in SEARCH_MODES:
+            raise ValueError(f"mode must be one of {', '.join(SEARCH_MODES)} (got {mode!r})")
+        if mode != "dense":
+            k = max(1, top_k)
+            hits = self._query_fused(query, k, k if reranker is None else max(k, candidates), mode)
+            if reranker is None or not hits:
+                return hits
+            top_k = k
+        else:
+            qv = self.embedder.embed([query])
+            if reranker is None:
+                return self.hits(self.search_vectors(qv, top_k)[0])
+            hits = self.hits(self.search_vectors(qv, max(top_k, candidates))[0])
         if not hits:
             return hits
         rs = [float(s) for s in reranker.score(query, [h.text for h in hits])]
@@ -295,6 +405,7 @@ class RagIndex:
         self._emb = list(emb)
         self._mat = emb if len(emb) else None
         self._gpu = None
+        self._lex = None  # not persisted: rebuilt from the texts on demand
         self.file_hashes = meta.get("file_hashes", {})
         return True
 
@@ -328,11 +439,12 @@ class RagIndex:
             embedded += len(chunks)
         self._mat = None
         self._gpu = None
+        self._lex = None
         self.save(cache_dir)
         return {"reused": reused, "embedded": embedded, "total": len(self.chunks)}
 
 
-__all__ = ["RagIndex", "RagChunk", "RagHit", "cosine_exact", "enumerate_files", "split_by_markdown_headers",
+__all__ = ["RagIndex", "RagChunk", "RagHit", "cosine_exact", "rrf_fuse", "enumerate_files", "split_by_markdown_headers",
            "chunk_sliding", "sanitize", "is_blank"]
 
 
