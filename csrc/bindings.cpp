@@ -517,8 +517,12 @@ void rope_kv_(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& co
 
 void kv_write(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at::Tensor& v_cache,
               const at::Tensor& slots) {
-  CHECK_CUDA(k); CHECK_BF16(k); CHECK_BF16(v); CHECK_I32(slots);
+  CHECK_CUDA(k); CHECK_CUDA(v); CHECK_CUDA(k_cache); CHECK_CUDA(v_cache); CHECK_CUDA(slots);
+  CHECK_BF16(k); CHECK_BF16(v); CHECK_BF16(k_cache); CHECK_BF16(v_cache); CHECK_I32(slots); CHECK_CONTIG(slots);
   TORCH_CHECK(k.dim() == 3 && v.sizes() == k.sizes(), "k/v must be [T, Hkv, D]");
+  TORCH_CHECK(slots.numel() == k.size(0), "slots must hold one entry per token");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "v_cache shape");
+  check_rows16(k, "k"); check_rows16(v, "v");
   TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == k.size(2) && v.stride(2) == 1 && v.stride(1) == v.size(2), "k/v inner layout");
   const int Hkv = k.size(1), D = k.size(2);
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == D && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache layout");

@@ -9,7 +9,9 @@ struct RowCfg {
 };
 inline RowCfg row_cfg(int H) {
   const int nvec = H / 8;
-  int nw = nvec >= 1024 ? 4 : (nvec >= 512 ? 4 : (nvec >= 256 ? 4 : (nvec >= 128 ? 2 : 1)));
+  // nvec 129..255 take 4 waves x 1 vector: 2 waves would need a (2 vectors, 2 waves) arm that
+  // ROW_DISPATCH does not have (every other H keeps the shape it always had)
+  int nw = nvec > 128 ? 4 : (nvec == 128 ? 2 : 1);
   int maxv = (nvec + nw * 64 - 1) / (nw * 64);
   return {nw, maxv};
 }

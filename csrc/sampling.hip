@@ -107,7 +107,9 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ lo
     if constexpr (KEY) {
       // high word: the max's float bits made order-preserving and signed; low word: ~global id
       // (the larger key is the larger value, then the lower id -- torch.argmax's tie order)
-      const unsigned fb = __float_as_uint(best == best ? best : -INFINITY);
+      // -0.0 is keyed as +0.0: gt() and torch.argmax hold them equal, so must the shards' keys
+      unsigned fb = __float_as_uint(best == best ? best : -INFINITY);
+      if (fb == 0x80000000u) fb = 0u;
       const unsigned u = (fb & 0x80000000u) ? ~fb : (fb | 0x80000000u);
       key_out[row] = (long long)(((unsigned long long)(u ^ 0x80000000u) << 32) | (unsigned)(~(unsigned)(bi + key_lo)));
     } else {

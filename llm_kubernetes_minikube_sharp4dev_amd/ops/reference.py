@@ -301,10 +301,14 @@ def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K):
 
 
 def pool_normalize(hidden, cu, mode, normalize):
+    """An empty sequence (cu[b] == cu[b + 1]) pools to zeros, as the kernel writes them."""
     cu = [int(x) for x in cu]
     outs = []
     for b in range(len(cu) - 1):
         h = hidden[cu[b]:cu[b + 1]].float()
+        if h.shape[0] == 0:
+            outs.append(h.new_zeros(hidden.shape[1]))
+            continue
         v = h[0] if mode == 1 else h.mean(0)
         if normalize:
             v = v / v.norm().clamp_min(1e-12)
@@ -357,9 +361,10 @@ def argmax_key(logits, vocab_lo: int = 0):
     """Order-preserving int64 (max value, ~(vocab_lo + first argmax)) key per row (the HIP
     kernel's encoding: csrc/sampling.hip select_kernel<..., KEY>)."""
     x = logits.float()
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)  # NaN counts as -inf
     idx = x.argmax(-1)
     best = x.gather(1, idx[:, None]).squeeze(1)
-    best = torch.where(torch.isnan(best), torch.full_like(best, float("-inf")), best)
+    best = torch.where(best == 0, torch.zeros_like(best), best)  # -0.0 is keyed as +0.0: they compare equal
     fb = best.view(torch.int32).long() & 0xFFFFFFFF
     u = torch.where(fb >= 0x80000000, (~fb) & 0xFFFFFFFF, fb | 0x80000000)
     hi = (u ^ 0x80000000) - ((u ^ 0x80000000) >= 0x80000000).long() * (1 << 32)  # signed 32-bit

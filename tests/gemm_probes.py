@@ -72,7 +72,10 @@ NORM_EPS = 1e-5
 def ulp(x):
     """Spacing of bf16 at |x| (float64 tensor): 2^(floor(log2 |x|) - 7); 0 at 0."""
     _, e = torch.frexp(x.abs())
-    return torch.where(x == 0, torch.zeros_like(x), torch.ldexp(torch.ones_like(x), e - 8))
+    # the power of two from its exponent bits: torch.ldexp is not exact on every device (2^-9 came out
+    # one float64 ulp short on the GPU, which turned exact ties of round_bf16 into near-ties)
+    p = ((e.long() + (1023 - 8)).clamp(1, 2046) << 52).view(torch.float64)
+    return torch.where(x == 0, torch.zeros_like(x), p)
 
 
 def round_bf16(e, mode="rne"):
