@@ -10,6 +10,13 @@ namespace {
 
 LK_DEVICE bool gt(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
 
+// u = (h + 0.5) * 2^-24 in (0, 1) for the top 24 bits h of a hash.  One FMA rounds the same real number
+// as the sum-then-scale it replaces, so every draw keeps its bits -- but for h = 0xFFFFFF the result
+// ties to even, 1.0f: the Gumbel noise -log(-log 1) is +inf and the id wins its row whatever its logit
+// (and u * kept mass reaches a trailing candidate of mass 0).  The cap moves that one draw to the
+// largest float below 1 and changes no other.
+LK_DEVICE float u01(unsigned hsh) { return fminf(fmaf((float)(hsh >> 8), 0x1p-24f, 0x1p-25f), 0x1.fffffep-1f); }
+
 LK_DEVICE unsigned hash3(unsigned a, unsigned b, unsigned c) {
   // splitmix-style avalanche over three words
   unsigned long long x = ((unsigned long long)a << 32) ^ ((unsigned long long)b * 0x9E3779B97F4A7C15ull) ^ c;
@@ -48,7 +55,7 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ lo
   auto consider = [&](float x, int idx) {
     if (!greedy) {
       const unsigned hsh = hash3((unsigned)(seed ^ (seed >> 32)) + row, (unsigned)step, (unsigned)idx);
-      const float u = ((float)(hsh >> 8) + 0.5f) * (1.f / 16777216.f);
+      const float u = u01(hsh);
       x = x * invt - __logf(-__logf(u));
     }
     if (gt(x, idx, best, bi)) {
@@ -240,6 +247,14 @@ LK_DEVICE unsigned fkey(float f) {  // order-preserving float -> uint
   const unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// fkey puts -0.0 (kNegZeroKey) one below +0.0, but gt(), torch.argmax and a stable sort hold the two
+// equal, and select_kernel's KEY arm keys them alike: a tie between them goes to the lower id.  So
+// every key that is sorted, or compared for equality, is zkey(fkey(x)).  The two passes over the whole
+// row (per-thread maxima, gather) stay on raw keys -- they are the cost of these kernels -- with a bound
+// of +0.0 lowered to -0.0, which gathers both zeros; zkey is applied to the gathered list before it is sorted.
+constexpr unsigned kNegZeroKey = 0x7FFFFFFFu, kPosZeroKey = 0x80000000u;
+LK_DEVICE unsigned zkey(unsigned k) { return k == kNegZeroKey ? kPosZeroKey : k; }
+LK_DEVICE unsigned zbound(unsigned t0) { return t0 == kPosZeroKey ? kNegZeroKey : t0; }
 constexpr unsigned kNegInfKey = 0x007FFFFFu;  // fkey(-inf); NaN with the sign bit below it
 LK_DEVICE float keyf(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
@@ -390,7 +405,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
   // -inf entries (a grammar mask) are never candidates: with fewer finite entries than K the
   // bound would otherwise be -inf and every masked entry would flood the candidate list and
   // the radix fallback's histograms (same-bin atomics).  k_eff below = min(K, finite ones).
-  const unsigned t0 = max(ckey[K - 1], kNegInfKey + 1u);
+  const unsigned t0 = zbound(max(ckey[K - 1], kNegInfKey + 1u));
   __syncthreads();
   // 2. gather every element >= t0
   for (int i = tid; i < V; i += kSampThreads) {
@@ -417,7 +432,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
       for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
       __syncthreads();
       for (int i = tid; i < V; i += kSampThreads) {
-        const unsigned k = fkey(lp[i]);
+        const unsigned k = zkey(fkey(lp[i]));
         if (k > kNegInfKey && (k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
       }
       __syncthreads();
@@ -442,7 +457,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
     if (tid == 0) ncand_s = 0;
     __syncthreads();
     for (int i = tid; i < V; i += kSampThreads) {
-      const unsigned k = fkey(lp[i]);
+      const unsigned k = zkey(fkey(lp[i]));
       if (k > prefix) {
         const int s = atomicAdd(&ncand_s, 1);
         ckey[s] = k;
@@ -453,7 +468,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
     int base = ncand_s, need = kr;
     for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
       const int i = c0 + tid;
-      const bool tie = i < V && fkey(lp[i]) == prefix;
+      const bool tie = i < V && zkey(fkey(lp[i])) == prefix;
       const int pos = (int)block_scan(tie ? 1.f : 0.f, wsum);  // ties up to and including this lane
       if (tie && pos <= need) {
         ckey[base + pos - 1] = prefix;
@@ -468,7 +483,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
     }
     nc = base;
   }
-  // 3. sort the candidates; the first K are the top K
+  // 3. sort the candidates; the first K are the top K  (the gathered keys are raw: -0.0 joins +0.0 here)
+  for (int i = tid; i < nc; i += kSampThreads) ckey[i] = zkey(ckey[i]);
   int n2 = 1;
   while (n2 < nc) n2 <<= 1;
   for (int i = nc + tid; i < n2; i += kSampThreads) {
@@ -504,7 +520,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
     // one draw per (request seed, generated-token position): reproducible per request, independent
     // of which batch row or engine step the sequence lands in
     const unsigned hsh = hash3((unsigned)(seed ^ (seed >> 32)), (unsigned)rseed, (unsigned)hl);
-    const float u = ((float)(hsh >> 8) + 0.5f) * (1.f / 16777216.f) * keep_s;
+    const float u = u01(hsh) * keep_s;  // u01 < 1: a kept candidate of mass 0 at the end of the list is never the pick
     // the first kept i whose inclusive prefix exceeds u
     __shared__ int pick_s;
     if (tid == 0) pick_s = nkeep_s - 1;
@@ -677,7 +693,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
 
   // 2. lower bound of the n-th largest value, then every element >= it
   bitonic(ckey, cidx, kSampThreads);
-  const unsigned t0 = ckey[n - 1];  // threads without elements hold key 0: a short row gathers whole
+  const unsigned t0 = zbound(ckey[n - 1]);  // threads without elements hold key 0: a short row gathers whole
   __syncthreads();
   lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
     const unsigned k = fkey(x);
@@ -703,7 +719,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
       for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
       __syncthreads();
       lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int) {
-        const unsigned k = fkey(x);
+        const unsigned k = zkey(fkey(x));
         if ((k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
       });
       __syncthreads();
@@ -727,7 +743,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
     if (tid == 0) ncand_s = 0;
     __syncthreads();
     lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
-      const unsigned k = fkey(x);
+      const unsigned k = zkey(fkey(x));
       if (k > prefix) {
         const int p = atomicAdd(&ncand_s, 1);
         if (p < kLpCand) {
@@ -740,7 +756,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
     int base = ncand_s, need = kr;
     for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
       const int i = c0 + tid;
-      const bool tie = i < V && fkey(at(i)) == prefix;
+      const bool tie = i < V && zkey(fkey(at(i))) == prefix;
       const int pos = block_scan_i(tie ? 1 : 0, iw);  // ties up to and including this thread
       if (tie && pos <= need) {
         ckey[base + pos - 1] = prefix;
@@ -755,7 +771,8 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
     }
     nc = base;
   }
-  // 3. sort the candidates; the first n are the top n
+  // 3. sort the candidates; the first n are the top n  (the gathered keys are raw: -0.0 joins +0.0 here)
+  for (int i = tid; i < nc; i += kSampThreads) ckey[i] = zkey(ckey[i]);
   int n2 = 1;
   while (n2 < nc) n2 <<= 1;
   for (int i = nc + tid; i < n2; i += kSampThreads) {
