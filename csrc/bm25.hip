@@ -31,23 +31,6 @@ constexpr int C = kLkBm25Chunk;
 constexpr int MAXT = kLkBm25MaxTerms;
 constexpr int PER = C / 256;
 
-// (score desc, index asc) ordering -- knn.hip's
-LK_DEVICE bool better(float s1, int i1, float s2, int i2) {
-  return s1 > s2 || (s1 == s2 && (unsigned)i1 < (unsigned)i2);
-}
-
-LK_DEVICE void wave_argmax(float& s, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s2 = __shfl_xor(s, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    if (better(s2, i2, s, i)) {
-      s = s2;
-      i = i2;
-    }
-  }
-}
-
 // first p in [lo, hi) with post_doc[p] >= key (hi if none)
 LK_DEVICE long lower_bound(const int* __restrict__ post_doc, long lo, long hi, long key) {
   while (lo < hi) {

@@ -23,23 +23,6 @@ namespace {
 constexpr int ROWS = 256;  // corpus rows per workgroup
 constexpr int QT = 32;     // queries per workgroup
 
-// (score desc, index asc) ordering
-LK_DEVICE bool better(float s1, int i1, float s2, int i2) {
-  return s1 > s2 || (s1 == s2 && (unsigned)i1 < (unsigned)i2);
-}
-
-LK_DEVICE void wave_argmax(float& s, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s2 = __shfl_xor(s, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    if (better(s2, i2, s, i)) {
-      s = s2;
-      i = i2;
-    }
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void knn_partial_kernel(
     const bf16_t* __restrict__ corpus, const float* __restrict__ cnorm, long N,

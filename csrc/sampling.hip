@@ -72,6 +72,8 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ lo
       else consider(reinterpret_cast<const float*>(logits)[(long)row * ls + id], id);
     }
   } else if constexpr (BF16) {
+    // (not lp_scan_row, the same walk: behind it the updates compile to exec-masked moves instead of
+    // selects, measured 3.6 % (Gumbel) and 6 % (greedy) slower: docs/sampling.md)
     const bf16_t* lp = reinterpret_cast<const bf16_t*>(logits) + (long)row * ls;
     for (int c = tid; c < nv; c += 256) {
       float v[8];
@@ -222,11 +224,8 @@ int lk_repeat_penalty(void* logits, int is_bf16, long ls, int B, const int* wind
 //     (hist[slot][*], the last min(len, last_n) tokens) is de-duplicated and applied to
 //     the f32 logits in place (l > 0 ? l / p : l * p).
 //   sample_topkp_kernel (1024 threads per row):
-//     1. each thread's max over its strided slice of the row; the K-th largest of the 1024
-//        maxima (bitonic sort in LDS) is a lower bound T0 of the row's K-th largest value;
-//     2. every element >= T0 is appended to an LDS candidate list (typically ~K of them;
-//        more than kCand -> exact radix select over the row in LDS histograms instead);
-//     3. bitonic sort of the candidates by (value desc, index asc) -> the top K;
+//     1. each thread's max over its strided slice of the row;
+//     2-3. top_n_sorted (below): the top K finite entries by (value desc, index asc);
 //     4. p_i = exp((v_i - v_0) / T), inclusive scan; keep i while the mass before it is
 //        <= top_p * total (so the token crossing top_p is kept); draw u from a counter-based
 //        hash of (request seed, generated-token position) and pick the first kept i with
@@ -331,18 +330,20 @@ __global__ __launch_bounds__(256) void sample_penalty_kernel(float* __restrict__
   }
 }
 
-// block-wide inclusive scan (1024 threads = 16 waves)
-LK_DEVICE float block_scan(float v, float* wsum) {
+// block-wide inclusive scan (1024 threads = 16 waves): a wave shuffle scan, then the serial sum of the
+// earlier waves' totals (for float this association is the one tests/sampler_probes.py models)
+template <class T>
+LK_DEVICE T block_scan(T v, T* wsum) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const float t = __shfl_up(v, o, 64);
+    const T t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
   }
   __syncthreads();
   if (lane == 63) wsum[w] = v;
   __syncthreads();
-  float add = 0.f;
+  T add = 0;
   for (int i = 0; i < w; ++i) add += wsum[i];
   return v + add;
 }
@@ -372,6 +373,147 @@ LK_DEVICE void bitonic(unsigned* key, int* idx, int n) {
   }
 }
 
+// f(value, index) for each element of the row this thread owns: 8-element chunks (16-byte loads) strided
+// over the workgroup plus a scalar tail (VEC: 16-byte-aligned rows), or a plain strided scan
+template <bool BF16, bool VEC, class F>
+LK_DEVICE void lp_scan_row(const void* rowp, int V, F&& f) {
+  const int tid = threadIdx.x;
+  const int nv = VEC ? V / 8 : 0;
+  if constexpr (BF16) {
+    const bf16_t* lp = reinterpret_cast<const bf16_t*>(rowp);
+    for (int c = tid; c < nv; c += kSampThreads) {
+      float v[8];
+      load8(lp + c * 8, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f(v[j], c * 8 + j);
+    }
+    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(bf2f(lp[i]), i);
+  } else {
+    const float* lp = reinterpret_cast<const float*>(rowp);
+    for (int c = tid; c < nv; c += kSampThreads) {
+      const float4 a = *reinterpret_cast<const float4*>(lp + c * 8);
+      const float4 b = *reinterpret_cast<const float4*>(lp + c * 8 + 4);
+      f(a.x, c * 8 + 0); f(a.y, c * 8 + 1); f(a.z, c * 8 + 2); f(a.w, c * 8 + 3);
+      f(b.x, c * 8 + 4); f(b.y, c * 8 + 5); f(b.z, c * 8 + 6); f(b.w, c * 8 + 7);
+    }
+    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(lp[i], i);
+  }
+}
+
+// The n largest elements of a row, sorted by (value desc, index asc), for one workgroup of kSampThreads:
+// shared by sample_topkp_kernel and token_logprobs_kernel.  On entry, behind a barrier, ckey[tid] is
+// the largest raw key of thread tid's elements, cidx[tid] = tid and sh.ncand = 0.
+//   bound:  the n-th largest of the 1024 thread maxima (bitonic sort in LDS) is a lower bound t0 of
+//           the row's n-th largest value (threads without elements hold key 0: a short row gathers whole);
+//   gather: every element >= t0 is appended to the CAP-entry candidate list (about n on real logits);
+//   radix:  more than CAP of them (a huge tie / plateau at or above t0) -> the exact n-th key by a
+//           3-digit MSB radix select over a 2048-bin LDS histogram, then the strictly larger keys
+//           (fewer than n) plus the lowest-index ties, chunk by chunk;
+//   sort:   -0.0 joins +0.0 (zkey), pad to a power of two, bitonic sort.
+// Returns the number of candidates nc, sorted in ckey / cidx; the first min(n, nc) are the answer.
+// scan(f) calls f(value, index) for each element this thread owns (lp_scan_row); at(i) is element i.
+// FINITE: -inf entries (a grammar mask) are never candidates: with fewer finite entries than n the
+// bound would otherwise be -inf and every masked entry would flood the candidate list and the
+// histograms (same-bin atomics); nc is then the number of finite entries.  Otherwise -inf takes part.
+struct TopNScratch {
+  int ncand, thr, above;  // candidate counter; the radix digit's threshold bin and the count above it
+  int wsum[16];
+};
+
+template <int CAP, bool FINITE, class Scan, class At>
+LK_DEVICE int top_n_sorted(unsigned* ckey, int* cidx, TopNScratch& sh, int n, int V, Scan&& scan, At&& at) {
+  static_assert(CAP >= kSampThreads && CAP >= 2048, "thread maxima and the radix histogram live in ckey");
+  const int tid = threadIdx.x;
+  bitonic(ckey, cidx, kSampThreads);
+  const unsigned t0 = zbound(FINITE ? max(ckey[n - 1], kNegInfKey + 1u) : ckey[n - 1]);
+  __syncthreads();
+  scan([&](float x, int i) {
+    const unsigned k = fkey(x);
+    if (k >= t0) {
+      const int p = atomicAdd(&sh.ncand, 1);
+      if (p < CAP) {
+        ckey[p] = k;
+        cidx[p] = i;
+      }
+    }
+  });
+  __syncthreads();
+  int nc = sh.ncand;
+  if (nc > CAP) {
+    unsigned* hst = ckey;  // reuse the candidate buffer as a 2048-bin histogram
+    unsigned prefix = 0, mask = 0;
+    int kr = n;
+    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
+    for (int d = 0; d < 3; ++d) {
+      const int nb = 1 << bits[d];
+      for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
+      __syncthreads();
+      scan([&](float x, int) {
+        const unsigned k = zkey(fkey(x));
+        if ((!FINITE || k > kNegInfKey) && (k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
+      });
+      __syncthreads();
+      // thread t owns bins 2047 - 2t and 2046 - 2t: the scan runs from the top bin down
+      const int hi = 2047 - 2 * tid;
+      const int c_hi = hi < nb ? (int)hst[hi] : 0, c_lo = hi - 1 < nb ? (int)hst[hi - 1] : 0;
+      const int incl = block_scan(c_hi + c_lo, sh.wsum);
+      const int excl = incl - (c_hi + c_lo);
+      if (excl < kr && incl >= kr) {
+        const int b = (excl + c_hi >= kr) ? hi : hi - 1;
+        sh.thr = b;
+        sh.above = excl + (b == hi ? 0 : c_hi);  // elements strictly above bin b
+      }
+      __syncthreads();
+      kr -= sh.above;
+      prefix |= (unsigned)sh.thr << shifts[d];
+      mask |= (unsigned)(nb - 1) << shifts[d];
+      __syncthreads();
+    }
+    // keys > prefix (n - kr of them, fewer than n), then the first kr ties in index order
+    if (tid == 0) sh.ncand = 0;
+    __syncthreads();
+    scan([&](float x, int i) {
+      const unsigned k = zkey(fkey(x));
+      if (k > prefix) {
+        const int p = atomicAdd(&sh.ncand, 1);
+        if (p < CAP) {
+          ckey[p] = k;
+          cidx[p] = i;
+        }
+      }
+    });
+    __syncthreads();
+    int base = sh.ncand, need = kr;
+    for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
+      const int i = c0 + tid;
+      const bool tie = i < V && zkey(fkey(at(i))) == prefix;
+      const int pos = block_scan(tie ? 1 : 0, sh.wsum);  // ties up to and including this thread
+      if (tie && pos <= need) {
+        ckey[base + pos - 1] = prefix;
+        cidx[base + pos - 1] = i;
+      }
+      if (tid == kSampThreads - 1) sh.thr = pos;  // ties in this chunk
+      __syncthreads();
+      const int taken = min(need, sh.thr);
+      base += taken;
+      need -= taken;
+      __syncthreads();
+    }
+    nc = base;
+  }
+  // the gathered keys are raw: -0.0 joins +0.0 here
+  for (int i = tid; i < nc; i += kSampThreads) ckey[i] = zkey(ckey[i]);
+  int n2 = 1;
+  while (n2 < nc) n2 <<= 1;
+  for (int i = nc + tid; i < n2; i += kSampThreads) {
+    ckey[i] = 0;
+    cidx[i] = 0x7fffffff;
+  }
+  __syncthreads();
+  bitonic(ckey, cidx, n2);
+  return nc;
+}
+
 // WIDE: 12-wide parameter rows; [8] = min_p joins the top-p cut in step 4
 template <bool WIDE>
 __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float* __restrict__ logits, long ls, int V,
@@ -382,7 +524,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
   __shared__ unsigned ckey[kCand];
   __shared__ int cidx[kCand];
   __shared__ float wsum[16];
-  __shared__ int ncand_s, thr_s, above_s;
+  __shared__ TopNScratch sh;
   const int row = blockIdx.x, tid = threadIdx.x;
   // (8-wide: the 32-bit offset this kernel always used.  A 64-bit one is an instruction shorter, moves
   // the sort loops 4 bytes and measured 0.5 % slower: docs/sampling.md)
@@ -394,106 +536,17 @@ __global__ __launch_bounds__(kSampThreads) void sample_topkp_kernel(const float*
   const int K = greedy ? 1 : min(top_k > 0 ? top_k : kSampKMax, min(V, kSampKMax));
   const float* lp = logits + (long)row * ls;
 
-  // 1. per-thread maxima -> lower bound of the K-th largest
+  // 1. per-thread maxima
   unsigned tmax = 0;
   for (int i = tid; i < V; i += kSampThreads) tmax = max(tmax, fkey(lp[i]));
   ckey[tid] = tmax;
   cidx[tid] = tid;
-  if (tid == 0) ncand_s = 0;
+  if (tid == 0) sh.ncand = 0;
   __syncthreads();
-  bitonic(ckey, cidx, kSampThreads);
-  // -inf entries (a grammar mask) are never candidates: with fewer finite entries than K the
-  // bound would otherwise be -inf and every masked entry would flood the candidate list and
-  // the radix fallback's histograms (same-bin atomics).  k_eff below = min(K, finite ones).
-  const unsigned t0 = zbound(max(ckey[K - 1], kNegInfKey + 1u));
-  __syncthreads();
-  // 2. gather every element >= t0
-  for (int i = tid; i < V; i += kSampThreads) {
-    const unsigned k = fkey(lp[i]);
-    if (k >= t0) {
-      const int s = atomicAdd(&ncand_s, 1);
-      if (s < kCand) {
-        ckey[s] = k;
-        cidx[s] = i;
-      }
-    }
-  }
-  __syncthreads();
-  int nc = ncand_s;
-  if (nc > kCand) {
-    // adversarial row (huge tie / plateau above t0): exact K-th key by a 3-digit MSB radix
-    // select with LDS histograms, then gather > threshold plus the lowest-index ties
-    unsigned* hst = ckey;  // reuse the candidate buffer as a 2048-bin histogram
-    unsigned prefix = 0, mask = 0;
-    int kr = K;
-    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
-    for (int d = 0; d < 3; ++d) {
-      const int nb = 1 << bits[d];
-      for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
-      __syncthreads();
-      for (int i = tid; i < V; i += kSampThreads) {
-        const unsigned k = zkey(fkey(lp[i]));
-        if (k > kNegInfKey && (k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
-      }
-      __syncthreads();
-      // thread t owns bins 2t', 2t'+1 counted from the top (t' = 1023 - t)
-      const int hi = 2047 - 2 * tid;
-      const float mine = (hi < nb ? (float)hst[hi] : 0.f) + (hi - 1 < nb && hi >= 1 ? (float)hst[hi - 1] : 0.f);
-      const float incl = block_scan(mine, wsum);
-      const float excl = incl - mine;
-      if (excl < kr && incl >= kr) {
-        const float c_hi = hi < nb ? (float)hst[hi] : 0.f;
-        const int b = (excl + c_hi >= kr) ? hi : hi - 1;
-        thr_s = b;
-        above_s = (int)(excl + (b == hi ? 0.f : c_hi));  // elements strictly above bin b
-      }
-      __syncthreads();
-      kr -= above_s;
-      prefix |= (unsigned)thr_s << shifts[d];
-      mask |= (unsigned)(nb - 1) << shifts[d];
-      __syncthreads();
-    }
-    // gather: key > prefix (K - kr of them), then the first kr ties in index order
-    if (tid == 0) ncand_s = 0;
-    __syncthreads();
-    for (int i = tid; i < V; i += kSampThreads) {
-      const unsigned k = zkey(fkey(lp[i]));
-      if (k > prefix) {
-        const int s = atomicAdd(&ncand_s, 1);
-        ckey[s] = k;
-        cidx[s] = i;
-      }
-    }
-    __syncthreads();
-    int base = ncand_s, need = kr;
-    for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
-      const int i = c0 + tid;
-      const bool tie = i < V && zkey(fkey(lp[i])) == prefix;
-      const int pos = (int)block_scan(tie ? 1.f : 0.f, wsum);  // ties up to and including this lane
-      if (tie && pos <= need) {
-        ckey[base + pos - 1] = prefix;
-        cidx[base + pos - 1] = i;
-      }
-      if (tid == kSampThreads - 1) thr_s = pos;  // ties in this chunk
-      __syncthreads();
-      const int taken = min(need, thr_s);
-      base += taken;
-      need -= taken;
-      __syncthreads();
-    }
-    nc = base;
-  }
-  // 3. sort the candidates; the first K are the top K  (the gathered keys are raw: -0.0 joins +0.0 here)
-  for (int i = tid; i < nc; i += kSampThreads) ckey[i] = zkey(ckey[i]);
-  int n2 = 1;
-  while (n2 < nc) n2 <<= 1;
-  for (int i = nc + tid; i < n2; i += kSampThreads) {
-    ckey[i] = 0;
-    cidx[i] = 0x7fffffff;
-  }
-  __syncthreads();
-  bitonic(ckey, cidx, n2);
-  const int k_eff = min(K, nc);
+  // 2-3. the top K finite entries, sorted (the plain strided scan, as in step 1)
+  const int nc = top_n_sorted<kCand, true>(
+      ckey, cidx, sh, K, V, [&](auto&& f) { lp_scan_row<false, false>(lp, V, f); }, [&](int i) { return lp[i]; });
+  const int k_eff = min(K, nc);  // fewer finite entries than K: all of them
   // 4. temperature softmax over the top K, top-p cut, inverse-CDF draw
   int tok;
   if (greedy || k_eff <= 1) {
@@ -570,58 +623,11 @@ int lk_sample(float* logits, long ls, int B, int V, const int* prm, int pw, cons
 //   1. one pass with 16-byte loads: each thread keeps an online (max, sum exp(x - max)) pair
 //      and the largest key of its elements; a butterfly + 16-wave combine gives the row
 //      maximum and log-sum-exp (exponents are only ever taken of x - a running maximum);
-//   2. the n-th largest of the 1024 per-thread maxima bounds the n-th largest value from
-//      below; a second pass appends every element >= it to an LDS candidate list (about n
-//      of them; a plateau of more than kLpCand -> the sampler's exact 3-digit radix select
-//      for the n-th key, then the strictly larger keys plus the lowest-index ties);
-//   3. bitonic sort of the candidates; the first n are the answer.  -inf entries take part
-//      (logprob -inf, after every finite value).
+//   2-3. top_n_sorted (above) with a kLpCand-entry candidate list: the top n by the same order, its
+//      row passes with 16-byte loads too.  -inf entries take part (logprob -inf, after every
+//      finite value).
 // Keys are compared on the loaded values themselves; the logits are never written.
 constexpr int kLpMaxN = 20, kLpCand = 2048;
-static_assert(kLpCand >= kSampThreads && kLpCand >= 2048, "thread maxima and the radix histogram live in ckey");
-
-// f(value, index) for each element of the row this thread owns: 8-element chunks strided over
-// the workgroup plus a scalar tail (VEC: 16-byte-aligned rows), or a plain strided scan
-template <bool BF16, bool VEC, class F>
-LK_DEVICE void lp_scan_row(const void* rowp, int V, F&& f) {
-  const int tid = threadIdx.x;
-  const int nv = VEC ? V / 8 : 0;
-  if constexpr (BF16) {
-    const bf16_t* lp = reinterpret_cast<const bf16_t*>(rowp);
-    for (int c = tid; c < nv; c += kSampThreads) {
-      float v[8];
-      load8(lp + c * 8, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f(v[j], c * 8 + j);
-    }
-    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(bf2f(lp[i]), i);
-  } else {
-    const float* lp = reinterpret_cast<const float*>(rowp);
-    for (int c = tid; c < nv; c += kSampThreads) {
-      const float4 a = *reinterpret_cast<const float4*>(lp + c * 8);
-      const float4 b = *reinterpret_cast<const float4*>(lp + c * 8 + 4);
-      f(a.x, c * 8 + 0); f(a.y, c * 8 + 1); f(a.z, c * 8 + 2); f(a.w, c * 8 + 3);
-      f(b.x, c * 8 + 4); f(b.y, c * 8 + 5); f(b.z, c * 8 + 6); f(b.w, c * 8 + 7);
-    }
-    for (int i = nv * 8 + tid; i < V; i += kSampThreads) f(lp[i], i);
-  }
-}
-
-// block-wide inclusive scan of counts (1024 threads = 16 waves)
-LK_DEVICE int block_scan_i(int v, int* wsum) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  __syncthreads();
-  if (lane == 63) wsum[w] = v;
-  __syncthreads();
-  int add = 0;
-  for (int i = 0; i < w; ++i) add += wsum[i];
-  return v + add;
-}
 
 // (max, sum exp(x - max)) of two partial rows; an empty part is (-FLT_MAX, 0)
 LK_DEVICE void lse_merge(float& m, float& s, float m2, float s2) {
@@ -640,8 +646,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
   __shared__ unsigned ckey[kLpCand];
   __shared__ int cidx[kLpCand];
   __shared__ float wm[16], ws[16];
-  __shared__ int iw[16];
-  __shared__ int ncand_s, thr_s, above_s;
+  __shared__ TopNScratch sh;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int row = rows[r];
   if (row < 0 || row >= B) {  // uniform per workgroup: a row outside the batch is never read
@@ -679,7 +684,7 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
   }
   ckey[tid] = tmax;
   cidx[tid] = tid;
-  if (tid == 0) ncand_s = 0;
+  if (tid == 0) sh.ncand = 0;
   __syncthreads();
   m = wm[0];
   s = ws[0];
@@ -691,96 +696,9 @@ __global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(const void
   }
   if (n == 0) return;  // uniform
 
-  // 2. lower bound of the n-th largest value, then every element >= it
-  bitonic(ckey, cidx, kSampThreads);
-  const unsigned t0 = zbound(ckey[n - 1]);  // threads without elements hold key 0: a short row gathers whole
-  __syncthreads();
-  lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
-    const unsigned k = fkey(x);
-    if (k >= t0) {
-      const int p = atomicAdd(&ncand_s, 1);
-      if (p < kLpCand) {
-        ckey[p] = k;
-        cidx[p] = i;
-      }
-    }
-  });
-  __syncthreads();
-  int nc = ncand_s;
-  if (nc > kLpCand) {
-    // a plateau at or above the bound: the exact n-th key by a 3-digit MSB radix select over LDS
-    // histograms (sample_topkp_kernel's scheme, -inf entries included), then gather
-    unsigned* hst = ckey;  // 2048 bins
-    unsigned prefix = 0, mask = 0;
-    int kr = n;
-    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
-    for (int d = 0; d < 3; ++d) {
-      const int nb = 1 << bits[d];
-      for (int b = tid; b < 2048; b += kSampThreads) hst[b] = 0;
-      __syncthreads();
-      lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int) {
-        const unsigned k = zkey(fkey(x));
-        if ((k & mask) == prefix) atomicAdd(&hst[(k >> shifts[d]) & (nb - 1)], 1u);
-      });
-      __syncthreads();
-      // thread t owns bins 2047 - 2t and 2046 - 2t: the scan runs from the top bin down
-      const int hi = 2047 - 2 * tid;
-      const int c_hi = hi < nb ? (int)hst[hi] : 0, c_lo = hi - 1 < nb ? (int)hst[hi - 1] : 0;
-      const int incl = block_scan_i(c_hi + c_lo, iw);
-      const int excl = incl - (c_hi + c_lo);
-      if (excl < kr && incl >= kr) {
-        const int b = (excl + c_hi >= kr) ? hi : hi - 1;
-        thr_s = b;
-        above_s = excl + (b == hi ? 0 : c_hi);  // elements strictly above bin b
-      }
-      __syncthreads();
-      kr -= above_s;
-      prefix |= (unsigned)thr_s << shifts[d];
-      mask |= (unsigned)(nb - 1) << shifts[d];
-      __syncthreads();
-    }
-    // keys > prefix (n - kr of them, fewer than n), then the first kr ties in index order
-    if (tid == 0) ncand_s = 0;
-    __syncthreads();
-    lp_scan_row<BF16, VEC>(rowp, V, [&](float x, int i) {
-      const unsigned k = zkey(fkey(x));
-      if (k > prefix) {
-        const int p = atomicAdd(&ncand_s, 1);
-        if (p < kLpCand) {
-          ckey[p] = k;
-          cidx[p] = i;
-        }
-      }
-    });
-    __syncthreads();
-    int base = ncand_s, need = kr;
-    for (int c0 = 0; c0 < V && need > 0; c0 += kSampThreads) {
-      const int i = c0 + tid;
-      const bool tie = i < V && zkey(fkey(at(i))) == prefix;
-      const int pos = block_scan_i(tie ? 1 : 0, iw);  // ties up to and including this thread
-      if (tie && pos <= need) {
-        ckey[base + pos - 1] = prefix;
-        cidx[base + pos - 1] = i;
-      }
-      if (tid == kSampThreads - 1) thr_s = pos;  // ties in this chunk
-      __syncthreads();
-      const int taken = min(need, thr_s);
-      base += taken;
-      need -= taken;
-      __syncthreads();
-    }
-    nc = base;
-  }
-  // 3. sort the candidates; the first n are the top n  (the gathered keys are raw: -0.0 joins +0.0 here)
-  for (int i = tid; i < nc; i += kSampThreads) ckey[i] = zkey(ckey[i]);
-  int n2 = 1;
-  while (n2 < nc) n2 <<= 1;
-  for (int i = nc + tid; i < n2; i += kSampThreads) {
-    ckey[i] = 0;
-    cidx[i] = 0x7fffffff;
-  }
-  __syncthreads();
-  bitonic(ckey, cidx, n2);
+  // 2-3. the top n, sorted
+  const int nc = top_n_sorted<kLpCand, false>(
+      ckey, cidx, sh, n, V, [&](auto&& f) { lp_scan_row<BF16, VEC>(rowp, V, f); }, at);
   if (tid < n) {
     const bool ok = tid < nc;  // always: the row has at least n elements
     top_lp[(long)r * n + tid] = ok ? (keyf(ckey[tid]) - rowmax) - logsum : __uint_as_float(0x7FC00000u);

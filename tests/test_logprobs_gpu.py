@@ -129,6 +129,21 @@ def test_plateau_forces_exact_fallback(hip, dtype):
     assert top_id[1].tolist() == [31000] + [int(i) for i in plateau[plateau != 31000][:4]]
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_zero_plateau_of_both_signs_forces_exact_fallback(hip, dtype):
+    """6192 zeros, -0.0 on odd ids, over a floor of -1.0: more than the candidate list holds, so
+    the radix select runs on a plateau whose two keys must count as one (the stable sort holds
+    -0.0 and +0.0 equal: the lowest ids lead)."""
+    V = 8192
+    x = torch.full((2, V), -1.0)
+    x[:, 2000:] = 0.0
+    x[:, 2001::2] = -0.0
+    x[1, 7000] = 1.0  # one element above the plateau: it leads, then the first four zeros
+    assert torch.signbit(x[0, 2001]) and not torch.signbit(x[0, 2000])
+    _, _, top_id = _check(x.to(dtype).to(DEV), [0, 1], 5)
+    assert top_id.tolist() == [[2000, 2001, 2002, 2003, 2004], [7000, 2000, 2001, 2002, 2003]]
+
+
 def test_neg_inf_entries(hip):
     torch.manual_seed(8)
     V = 20000
