@@ -237,15 +237,17 @@ def cosine_scores(corpus, cnorm, queries, qnorm, eps=1e-9):
 
 
 def stable_topk(scores, K):
-    """Descending scores, ties by ascending index (C# OrderByDescending is stable)."""
+    """Descending scores, ties by ascending index (C# OrderByDescending is stable).  A NaN score is
+    absent, as in the kernels (where NaN is never better than anything): the row is left out and
+    (-inf, -1) pads follow."""
     nq, N = scores.shape
-    K_eff = min(K, N)
     out_s = torch.full((nq, K), float("-inf"), dtype=torch.float32)
     out_i = torch.full((nq, K), -1, dtype=torch.int32)
     for i in range(nq):
-        order = sorted(range(N), key=lambda j: (-float(scores[i, j]), j))[:K_eff]
-        out_i[i, :K_eff] = torch.tensor(order, dtype=torch.int32)
-        out_s[i, :K_eff] = scores[i, order].float()
+        row = scores[i].tolist()
+        order = sorted((j for j in range(N) if row[j] == row[j]), key=lambda j: (-row[j], j))[:K]
+        out_i[i, : len(order)] = torch.tensor(order, dtype=torch.int32)
+        out_s[i, : len(order)] = scores[i, order].float()
     return out_s, out_i
 
 
