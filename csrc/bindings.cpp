@@ -464,6 +464,53 @@ at::Tensor gather_rows(const at::Tensor& x, const at::Tensor& idx) {
   return out;
 }
 
+// The rows idx of a step, compacted in one launch: x [T, H] -> [R, H]; x2 [T, H2] likewise;
+// ss [P, >= T] f32 -> columns idx into [P, ss_ld_out >= R] (or into ss_out [P, >= R], whose columns
+// from R on are left as they are); pos [>= T] i32 -> [R].
+// Returns (x rows, x2 rows, ss planes, positions), an undefined tensor for every absent source.
+std::vector<at::Tensor> gather_step(const at::Tensor& idx, const at::Tensor& x, const c10::optional<at::Tensor>& x2,
+                                    const c10::optional<at::Tensor>& ss, const c10::optional<at::Tensor>& pos,
+                                    int64_t ss_ld_out, const c10::optional<at::Tensor>& ss_out) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_LASTDIM(x); check_rows16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) % 8 == 0 && x.size(1) >= 8, "x [T >= 1, H], H % 8");
+  CHECK_CUDA(idx);
+  TORCH_CHECK(idx.scalar_type() == at::kLong && idx.is_contiguous() && idx.dim() == 1, "idx int64 [R]");
+  const int64_t R = idx.numel(), T = x.size(0);
+  at::Tensor xo = at::empty({R, x.size(1)}, x.options()), x2o, sso, poso;
+  const bf16_t* b = nullptr; bf16_t* bo = nullptr; long b_ld = 0; int Hb = 0;
+  if (x2) {
+    CHECK_CUDA(*x2); CHECK_BF16(*x2); CHECK_LASTDIM(*x2); check_rows16(*x2, "x2");
+    TORCH_CHECK(x2->dim() == 2 && x2->size(0) >= T && x2->size(1) % 8 == 0 && x2->size(1) >= 8, "x2 [>= T, H2], H2 % 8");
+    x2o = at::empty({R, x2->size(1)}, x2->options());
+    b = bp(*x2); bo = bp(x2o); b_ld = x2->stride(0); Hb = x2->size(1);
+  }
+  const float* sp = nullptr; float* spo = nullptr; long s_ld = 0; int planes = 0;
+  if (ss) {
+    CHECK_CUDA(*ss); CHECK_F32(*ss); CHECK_CONTIG(*ss);
+    TORCH_CHECK(ss->dim() == 2 && ss->size(0) >= 1 && ss->size(1) >= T, "ss [P, >= T] f32");
+    if (ss_out) {
+      CHECK_CUDA(*ss_out); CHECK_F32(*ss_out); CHECK_CONTIG(*ss_out);
+      TORCH_CHECK(ss_out->dim() == 2 && ss_out->size(0) == ss->size(0) && ss_out->size(1) >= R, "ss_out [P, >= R] f32");
+      sso = *ss_out;
+    } else {
+      const int64_t ld = std::max<int64_t>(std::max<int64_t>(ss_ld_out, R), 1);
+      sso = at::empty({ss->size(0), ld}, ss->options());
+    }
+    sp = ss->data_ptr<float>(); spo = sso.data_ptr<float>(); s_ld = ss->size(1); planes = ss->size(0);
+  }
+  const int* pp = nullptr; int* ppo = nullptr;
+  if (pos) {
+    CHECK_CUDA(*pos); CHECK_I32(*pos); CHECK_CONTIG(*pos);
+    TORCH_CHECK(pos->numel() >= T, "pos [>= T]");
+    poso = at::empty({R}, pos->options());
+    pp = ip(*pos); ppo = poso.data_ptr<int>();
+  }
+  CHECK_RC(lk_gather_step(idx.data_ptr<int64_t>(), R, T, bp(x), x.stride(0), bp(xo), x.size(1), b, b_ld, bo, Hb, sp, s_ld,
+                          spo, sso.defined() ? sso.size(1) : 0, planes, pp, ppo, cur_stream()),
+           "gather_step");
+  return {xo, x2o, sso, poso};
+}
+
 int64_t gemm_streamk(int64_t mode) { return lk_gemm_streamk((int)mode); }
 
 bool gemm_supported(int64_t M, int64_t N, int64_t K, int64_t epi, int64_t bn, int64_t splits, int64_t variant) {
@@ -1140,6 +1187,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "token ids outside the (whole) embedding table seen since the last call (resets)");
   m.def("scatter_ids", &scatter_ids);
   m.def("gather_rows", &gather_rows);
+  m.def("gather_step", &gather_step, "", py::arg("idx"), py::arg("x"), py::arg("x2") = py::none(), py::arg("ss") = py::none(),
+        py::arg("pos") = py::none(), py::arg("ss_ld_out") = 0, py::arg("ss_out") = py::none());
   m.def("argmax_key", &argmax_key, "", py::arg("logits"), py::arg("vocab_lo") = 0);
   m.def("keys_to_ids", &keys_to_ids);
   m.def("gemm_streamk", &gemm_streamk,

@@ -253,3 +253,10 @@ int lk_embed_rows(bf16_t* out, const bf16_t* table, const int* ids, long T, int 
 int lk_embed_errors();  // out-of-table ids seen by strict lk_embed_rows since the last call
 int lk_scatter_ids(int* ids, const long* dst, const int* prev, const long* src, int n, hipStream_t st);
 int lk_gather_rows(bf16_t* out, const bf16_t* x, long xs, const long* idx, long R, int H, hipStream_t st);
+// The rows idx[0 .. R) (each in [0, T); any other index gives zeros) of a step, compacted in one
+// launch; every source is optional (nullptr): a_out[r, :] = a[idx[r], :] (Ha bf16, row stride
+// a_ld; a_out dense), b likewise, ss_out[p * ss_out_ld + r] = ss[p * ss_ld + idx[r]] for the
+// `planes` partial-sum planes of the folded norm, pos_out[r] = pos[idx[r]].
+int lk_gather_step(const long* idx, long R, long T, const bf16_t* a, long a_ld, bf16_t* a_out, int Ha, const bf16_t* b,
+                   long b_ld, bf16_t* b_out, int Hb, const float* ss, long ss_ld, float* ss_out, long ss_out_ld,
+                   int planes, const int* pos, int* pos_out, hipStream_t st);

@@ -1,7 +1,9 @@
 // Small per-step data movement of the engine's forward, so a steady-state step runs no
 // framework (at::native) kernels: the embedding gather from int32 token ids (vocab-parallel
 // masked form included), the in-flight decode-id gather of pipelined steps, and the row gather
-// of the hidden states that feed the LM head.  Each is one launch of 16-B vector copies.
+// of the hidden states that feed the LM head, and the compaction of the rows the last decoder
+// layer still computes (residual / attention rows, their sum-of-squares planes and positions).
+// Each is one launch of 16-B vector copies.
 #include "common.h"
 #include "kernels.h"
 
@@ -47,6 +49,54 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(bf16_t* __restrict__ o
   *reinterpret_cast<uint4_t*>(out + r * H + c * 8) = *reinterpret_cast<const uint4_t*>(x + idx[r] * xs + c * 8);
 }
 
+// The last layer's rows: work item i copies one 16-B vector of an `a` row, then of a `b` row, then
+// one plane entry, then one position (four ranges of one flat index; absent parts are empty).
+struct GatherStep {
+  const long* idx;
+  long R, T;
+  const bf16_t* a; long a_ld; bf16_t* a_out; int va;  // va = Ha / 8 vectors per row
+  const bf16_t* b; long b_ld; bf16_t* b_out; int vb;
+  const float* ss; long ss_ld; float* ss_out; long ss_out_ld; int planes;
+  const int* pos; int* pos_out;
+};
+
+__global__ __launch_bounds__(256) void gather_step_kernel(GatherStep g) {
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long na = g.R * g.va, nb = g.R * g.vb, ns = g.R * g.planes;
+  const uint4_t zero = {0u, 0u, 0u, 0u};
+  if (i < na) {
+    const long r = i / g.va;
+    const int c = (int)(i - r * g.va);
+    const long s = g.idx[r];
+    const bool ok = s >= 0 && s < g.T;
+    *reinterpret_cast<uint4_t*>(g.a_out + (r * g.va + c) * 8) =
+        ok ? *reinterpret_cast<const uint4_t*>(g.a + s * g.a_ld + c * 8) : zero;
+    return;
+  }
+  i -= na;
+  if (i < nb) {
+    const long r = i / g.vb;
+    const int c = (int)(i - r * g.vb);
+    const long s = g.idx[r];
+    const bool ok = s >= 0 && s < g.T;
+    *reinterpret_cast<uint4_t*>(g.b_out + (r * g.vb + c) * 8) =
+        ok ? *reinterpret_cast<const uint4_t*>(g.b + s * g.b_ld + c * 8) : zero;
+    return;
+  }
+  i -= nb;
+  if (i < ns) {
+    const long p = i / g.R, r = i - p * g.R;
+    const long s = g.idx[r];
+    g.ss_out[p * g.ss_out_ld + r] = s >= 0 && s < g.T ? g.ss[p * g.ss_ld + s] : 0.f;
+    return;
+  }
+  i -= ns;
+  if (i < g.R && g.pos != nullptr) {
+    const long s = g.idx[i];
+    g.pos_out[i] = s >= 0 && s < g.T ? g.pos[s] : 0;
+  }
+}
+
 }  // namespace
 
 int lk_embed_rows(bf16_t* out, const bf16_t* table, const int* ids, long T, int H, long lo, long n_local,
@@ -84,5 +134,26 @@ int lk_gather_rows(bf16_t* out, const bf16_t* x, long xs, const long* idx, long 
   if (R == 0) return 0;
   const long n = R * (H / 8);
   gather_rows_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(out, x, xs, idx, R, H);
+  return 0;
+}
+
+int lk_gather_step(const long* idx, long R, long T, const bf16_t* a, long a_ld, bf16_t* a_out, int Ha, const bf16_t* b,
+                   long b_ld, bf16_t* b_out, int Hb, const float* ss, long ss_ld, float* ss_out, long ss_out_ld,
+                   int planes, const int* pos, int* pos_out, hipStream_t st) {
+  if (idx == nullptr || R < 0 || T < 1) return -1;
+  if (a == nullptr) Ha = 0;
+  if (b == nullptr) Hb = 0;
+  if (ss == nullptr) planes = 0;
+  if ((a && (!a_out || Ha < 8 || Ha % 8 || a_ld % 8 || a_ld < Ha)) || (b && (!b_out || Hb < 8 || Hb % 8 || b_ld % 8 || b_ld < Hb)))
+    return -1;
+  if (ss && (!ss_out || planes < 1 || ss_ld < T || ss_out_ld < R)) return -1;
+  if (pos && !pos_out) return -1;
+  if (R == 0) return 0;
+  GatherStep g{idx, R, T, a, a_ld, a_out, Ha / 8, b, b_ld, b_out, Hb / 8, ss, ss_ld, ss_out, ss_out_ld, planes, pos, pos_out};
+  const long n = R * (g.va + g.vb + planes + (pos ? 1 : 0));
+  if (n == 0) return 0;
+  if (n > 0x7FFFFFFFL * 256) return -1;
+  gather_step_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(g);
+  LK_CHECK_LAUNCH();
   return 0;
 }

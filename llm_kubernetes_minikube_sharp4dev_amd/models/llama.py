@@ -62,6 +62,16 @@ TP_OVERLAP_CHUNKS = int(os.environ.get("LK_TP_OVERLAP_CHUNKS", "2"))
 TP_OVERLAP_ALIGN = int(os.environ.get("LK_TP_OVERLAP_ALIGN", "256"))
 
 
+# The last decoder block of a prefill-sized step (``_forward_chain``): after attention only the
+# rows that feed the LM head (``meta.logits_idx``) go on -- every other row has already given the
+# layer all the step keeps of it, its K / V in the paged cache -- so O, gate_up and down run on
+# those rows, gathered, through the kernel the whole step would use (bit-identical hidden rows).
+# LK_LAST_LAYER_ROWS=0: every row, as before.  Steps whose logit rows are at least half of the rows,
+# or more than LAST_LAYER_MAX_ROWS, keep the full path.
+LAST_LAYER_ROWS = os.environ.get("LK_LAST_LAYER_ROWS", "1") != "0"
+LAST_LAYER_MAX_ROWS = 512
+
+
 def overlap_chunks(T: int, chunks: int = None, align: int = None, min_rows: int = None) -> Optional[list]:
     """[(r0, r1)] row chunks of a T-row row-parallel tail (None: do not chunk)."""
     chunks = TP_OVERLAP_CHUNKS if chunks is None else chunks
@@ -122,6 +132,7 @@ class LlamaModel(nn.Module):
         self.sp_min_tokens: Optional[int] = int(sp) if sp else None
         self._comm_stream = None  # TP prefill: the row-parallel tails' stream (_post_attn_pipelined)
         self.overlap_tails = 0    # layers whose post-attention half ran chunked + overlapped
+        self.last_layer_rows = 0  # steps whose last block ran on the gathered logit rows only
         # RoPE pairs: rotate_half (i, i + D/2) as in HF checkpoints, or adjacent (2i, 2i + 1) once
         # fold_norms has permuted the q / k rows (what the fused QKV epilogue rotates)
         self.rope_neox = True
@@ -316,18 +327,52 @@ class LlamaModel(nn.Module):
         ss_in = ops.ss_buffer(T, H, res.device)
         x, scale = ops.rmsnorm(res, self.layers[0].input_norm, eps), None
         attn_out = None
+        rows = self._last_layer_plan(res, meta)
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]
             qkv = ops.linear_qkv_fused(x, L.qkv, scale, eps, meta.positions, self.cos_sin, self.hq, self.hkv,
                                        self.D, kc, vc, meta.slots)
             attn_out = paged_attention(qkv, kc, vc, meta, self.hq, self.hkv, self.D, self.scale, attn_out,
                                        cp_group=self.cp_group)
+            if rows is not None and li + 1 == len(self.layers):
+                return self._last_layer_tail(L, res, attn_out, meta.logits_idx, rows)
             ops.linear_resid(attn_out, L.o, res, ss_post)
             a = ops.linear_swiglu_scaled(res, L.gate_up, ss_post, eps)
             ops.linear_resid(a, L.down, res, ss_in)
             x, scale = res, ss_in
         h = res if meta.logits_idx is None else ops.gather_rows(res, meta.logits_idx)
         return ops.rmsnorm(h, self.final_norm, eps)
+
+    def _last_layer_plan(self, res: torch.Tensor, meta: AttnMeta):
+        """The (O, gate_up, down) GEMM configurations of the last block's gathered rows, or None:
+        the block runs every row (switch off, no or too many logit rows, or a projection the whole
+        step would not run on the unsplit one-wave GEMM, whose sums the gathered rows must repeat)."""
+        idx = meta.logits_idx
+        if not LAST_LAYER_ROWS or idx is None:
+            return None
+        T, R = res.shape[0], idx.shape[0]
+        if R < 1 or 2 * R >= T or R > LAST_LAYER_MAX_ROWS:
+            return None
+        if not ops.use_hip(res):
+            return (None, None, None)  # reference ops: no kernel to choose
+        L = self.layers[-1]
+        cfgs = tuple(ops.rows_cfg(T, R, w.shape[0], w.shape[1], epi) for w, epi in ((L.o, 0), (L.gate_up, 1), (L.down, 0)))
+        return None if any(c is None for c in cfgs) else cfgs
+
+    def _last_layer_tail(self, L, res: torch.Tensor, attn_out: torch.Tensor, idx: torch.Tensor, cfgs) -> torch.Tensor:
+        """The last block after attention, on the rows ``idx`` alone, in their order: gather the
+        residual and the attention rows, O -> gate_up -> down on the compact buffers, final norm
+        (what ``gather_rows`` of the full block's residual, then the norm, gives)."""
+        self.last_layer_rows += 1
+        eps = self.cfg.norm_eps
+        R, H = idx.shape[0], res.shape[1]
+        res_c, attn_c, _, _ = ops.gather_step(idx, res, attn_out)
+        ss_post = ops.ss_buffer(R, H, res.device)
+        ss_in = ops.ss_buffer(R, H, res.device)
+        ops.linear_resid(attn_c, L.o, res_c, ss_post, cfg=cfgs[0])
+        a = ops.linear_swiglu_scaled(res_c, L.gate_up, ss_post, eps, cfg=cfgs[1])
+        ops.linear_resid(a, L.down, res_c, ss_in, cfg=cfgs[2])
+        return ops.rmsnorm(res_c, self.final_norm, eps)
 
     def _forward_sp(self, ids: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
         """Sequence-parallel forward: this rank keeps rows [r*n, (r+1)*n) of the

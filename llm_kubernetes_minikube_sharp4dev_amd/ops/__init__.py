@@ -1066,24 +1066,25 @@ def ss_buffer(M: int, N: int, device) -> torch.Tensor:
     return torch.empty((N // 256, M), dtype=torch.float32, device=device)
 
 
-def linear_resid(x, w, residual, ss_out):
+def linear_resid(x, w, residual, ss_out, cfg=None):
     """residual += x W^T (bf16 rounding as the unfused linear -> add), and the partial sums of
-    squares of the new residual per 256 columns into ss_out [N / 256, >= M] (one GEMM)."""
+    squares of the new residual per 256 columns into ss_out [N / 256, >= M] (one GEMM).
+    ``cfg``: an explicit (variant, bn, splits) instead of the dispatch's."""
     if not use_hip(x):
         return ref.linear_resid(x, w, residual, ss_out)
     M, K = x.shape
     N = w.shape[0]
-    sched, bn, ks = _resid_cfg(M, N, K)
+    sched, bn, ks = cfg if cfg is not None else _resid_cfg(M, N, K)
     return lib().gemm_fused(x, w, EPI_RESID, bn, None, sched, ks, resid=residual, ss_out=ss_out)
 
 
-def linear_swiglu_scaled(x, w_gate_up, ss, eps: float):
+def linear_swiglu_scaled(x, w_gate_up, ss, eps: float, cfg=None):
     """silu(s * x Wg^T) * (s * x Wu^T), s = the folded norm's per-row rsqrt from ``ss``."""
     if not use_hip(x):
         return ref.gemm_scaled(x, w_gate_up, ss, x.shape[1], eps, swiglu=True)
     M, K = x.shape
     N = w_gate_up.shape[0]
-    sched, bn, _ = _cfg_of(M, N, K, 1)
+    sched, bn, _ = cfg if cfg is not None else _cfg_of(M, N, K, 1)
     return lib().gemm_fused(x, w_gate_up, 1, bn, None, sched, 1, ss_in=ss, eps=eps)
 
 
@@ -1098,6 +1099,33 @@ def linear_qkv_fused(x, w, ss, eps: float, positions, cos_sin, Hq: int, Hkv: int
     sched, bn, _ = _cfg_of(M, N, K, 0)
     return lib().gemm_fused(x, w, EPI_QKV, bn, None, sched, 1, ss_in=ss, eps=eps, positions=positions,
                             cos_sin=cos_sin, slots=slots, k_cache=k_cache, v_cache=v_cache, hq=Hq, hkv=Hkv, hd=D)
+
+
+# ---------------------------------------------------------------- the last layer's rows
+# After the last decoder block only the rows that feed the LM head are read (models/llama.py
+# _forward_chain); they run through the SAME kernel as the whole step would -- gemm1w.hip,
+# unsplit, whose result for a row does not depend on the row tile or on the other rows -- so the
+# hidden states are the whole step's, bit for bit.  The weight-streaming and split-K kernels sum
+# in another order and are not used for them.
+def rows_cfg(M: int, R: int, N: int, K: int, epi: int):
+    """(variant, 256, 1) for R gathered rows of an M-row step's projection, or None when the
+    whole step would not run it on gemm1w.hip unsplit (then the gathered rows must not either)."""
+    c = _cfg_of(M, N, K, epi) if epi == 1 else _resid_cfg(M, N, K)
+    if c is None or c[0] not in GEMM1W_BM or c[1] != 256 or c[2] != 1:
+        return None
+    v = 5 if R <= 256 else 3  # 128-row tiles: at most 2 x N / 256 tiles, under one wave of the CUs
+    if not lib().gemm_supported(R, N, K, EPI_RESID if epi == 0 else epi, 256, 1, v):
+        return None
+    return (v, 256, 1)
+
+
+def gather_step(idx, x, x2=None, ss=None, pos=None, ss_ld: int = 0, ss_out=None):
+    """Rows ``idx`` (int64 [R]) of a step in one launch: (x[idx], x2[idx] or None, the columns idx
+    of the sum-of-squares planes ss [P, >= T] as [P, max(ss_ld, R)] -- or in the first R columns
+    of ``ss_out`` [P, >= R] -- or None, pos[idx] or None)."""
+    if use_hip(x) and x.dtype == torch.bfloat16 and idx.dtype == torch.int64:
+        return tuple(lib().gather_step(idx.contiguous(), x, x2, ss, pos, ss_ld, ss_out))
+    return ref.gather_step(idx, x, x2, ss, pos, ss_ld, ss_out)
 
 
 # ---------------------------------------------------------------- per-step gathers (csrc/step_ops.hip)

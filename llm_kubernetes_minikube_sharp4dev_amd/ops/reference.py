@@ -537,9 +537,15 @@ def row_scale(ss: torch.Tensor, H: int, eps: float) -> torch.Tensor:
     return torch.rsqrt(ss.float().sum(0) / H + eps)
 
 
+def _mm(x, w):
+    """x w^T in fp32: the product of the fused-chain oracles below (one place, so a test can pin
+    its summation order per row: the library's depends on the number of rows)."""
+    return x.float() @ w.float().t()
+
+
 def linear_resid(x, w, residual, ss_out):
     """residual = bf16(residual + bf16(x w^T)) in place; ss_out [N/256, >= M] = its partials."""
-    y = (x.float() @ w.float().t()).to(x.dtype)
+    y = _mm(x, w).to(x.dtype)
     residual.copy_((residual.float() + y.float()).to(residual.dtype))
     M = residual.shape[0]
     ss_out[:, :M] = ss_partials(residual)
@@ -549,7 +555,7 @@ def linear_resid(x, w, residual, ss_out):
 def gemm_scaled(x, w, ss, H, eps, swiglu=False):
     """x w^T with each row scaled by the folded norm's rsqrt (ss None: unscaled); SwiGLU:
     silu(g) * u on the scaled, bf16-rounded halves."""
-    acc = x.float() @ w.float().t()
+    acc = _mm(x, w)
     if ss is not None:
         acc = acc * row_scale(ss, H, eps)[: x.shape[0], None]
     if not swiglu:
@@ -564,3 +570,16 @@ def qkv_fused(x, w, ss, H, eps, positions, cos_sin, Hq, Hkv, D, k_cache=None, v_
     q and k (written back into the row), K / V into the paged cache."""
     qkv = gemm_scaled(x, w, ss, H, eps)
     return rope_kv_(qkv, positions, cos_sin, Hq, Hkv, D, k_cache, v_cache, slots, neox=False, write_k_inplace=True)
+
+
+def gather_step(idx, x, x2=None, ss=None, pos=None, ss_ld=0, ss_out=None):
+    """ops.gather_step: rows idx of x / x2, columns idx of the planes ss, pos[idx]."""
+    i = idx.long()
+    R = i.numel()
+    ss_c = None
+    if ss is not None:
+        ss_c = ss_out if ss_out is not None else torch.zeros(ss.shape[0], max(ss_ld, R, 1), dtype=ss.dtype,
+                                                             device=ss.device)
+        ss_c[:, :R] = ss.index_select(1, i)
+    return (x.index_select(0, i), None if x2 is None else x2.index_select(0, i), ss_c,
+            None if pos is None else pos.index_select(0, i))
