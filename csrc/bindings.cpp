@@ -797,6 +797,36 @@ std::vector<at::Tensor> bm25_topk(const at::Tensor& term_ptr, const at::Tensor& 
   return {out_s, out_i};
 }
 
+// MMR selection over candidate lists (csrc/mmr.hip): -> (pos int32, ids int32, rel f32, mmr f32,
+// max_sim f32), each [nq, K].  Every limit is refused here, by the argument's name, before a launch.
+std::vector<at::Tensor> mmr_select(const at::Tensor& corpus, const at::Tensor& cnorm, const at::Tensor& cand_id,
+                                   const at::Tensor& rel, double lam, int64_t K) {
+  CHECK_CUDA(corpus); CHECK_BF16(corpus); CHECK_CONTIG(corpus); CHECK_CUDA(cnorm); CHECK_F32(cnorm); CHECK_CONTIG(cnorm);
+  CHECK_CUDA(cand_id); CHECK_I32(cand_id); CHECK_CONTIG(cand_id); CHECK_CUDA(rel); CHECK_F32(rel); CHECK_CONTIG(rel);
+  TORCH_CHECK(corpus.dim() == 2, "mmr_select: corpus must be [N, D]");
+  const int64_t N = corpus.size(0), D = corpus.size(1);
+  TORCH_CHECK(cnorm.dim() == 1 && cnorm.numel() == N, "mmr_select: cnorm must be [N]");
+  TORCH_CHECK(cand_id.dim() == 2 && rel.dim() == 2 && cand_id.sizes() == rel.sizes(),
+              "mmr_select: cand_id and rel must have the same shape [nq, C]");
+  const int64_t nq = cand_id.size(0), C = cand_id.size(1);
+  TORCH_CHECK(C >= 1 && C <= kLkMmrMaxCand, "mmr_select: C (the width of cand_id) must be in [1, ", kLkMmrMaxCand, "] (got ", C, ")");
+  TORCH_CHECK(K >= 1 && K <= C, "mmr_select: K must be in [1, C = ", C, "] (got ", K, ")");
+  TORCH_CHECK(D % 16 == 0 && D >= 16 && D <= 1024, "mmr_select: D must be a multiple of 16 in [16, 1024] (got ", D, ")");
+  TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "mmr_select: lam must be a finite number in [0, 1] (got ", lam, ")");
+  TORCH_CHECK(N < (1LL << 31), "mmr_select: N must be below 2^31 (got ", N, ")");
+  TORCH_CHECK(nq < (1LL << 31), "mmr_select: nq must be below 2^31 (got ", nq, ")");
+  check_rows16(corpus, "corpus");
+  auto fo = corpus.options().dtype(at::kFloat);
+  auto io = corpus.options().dtype(at::kInt);
+  at::Tensor pos = at::empty({nq, K}, io), ids = at::empty({nq, K}, io);
+  at::Tensor ro = at::empty({nq, K}, fo), mmr = at::empty({nq, K}, fo), ms = at::empty({nq, K}, fo);
+  int rc = lk_mmr_select(bp(corpus), cnorm.data_ptr<float>(), N, (int)D, ip(cand_id), rel.data_ptr<float>(), (int)nq,
+                         (int)C, (float)lam, (int)K, pos.data_ptr<int>(), ids.data_ptr<int>(), ro.data_ptr<float>(),
+                         mmr.data_ptr<float>(), ms.data_ptr<float>(), cur_stream());
+  CHECK_RC(rc, "mmr_select");
+  return {pos, ids, ro, mmr, ms};
+}
+
 // out: optional destination rows [B, H] (f32 or bf16, unit last stride, 16-byte rows), e.g. a
 // slice of the caller's embedding matrix; default a new f32 [B, H]
 at::Tensor pool_normalize(const at::Tensor& hidden, const at::Tensor& cu, int64_t mode, bool normalize,
@@ -1233,6 +1263,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q_ptr"), py::arg("q_term"), py::arg("q_w"), py::arg("K"));
   m.attr("BM25_CHUNK") = kLkBm25Chunk;
   m.attr("BM25_MAX_TERMS") = kLkBm25MaxTerms;
+  m.def("mmr_select", &mmr_select, "", py::arg("corpus"), py::arg("cnorm"), py::arg("cand_id"), py::arg("rel"),
+        py::arg("lam"), py::arg("K"));
+  m.attr("MMR_MAX_CAND") = kLkMmrMaxCand;
   m.def("pool_normalize", &pool_normalize, "", py::arg("hidden"), py::arg("cu"), py::arg("mode"), py::arg("normalize"),
         py::arg("out") = py::none());
   m.def("rerank_head", &rerank_head, "", py::arg("hidden"), py::arg("cu"), py::arg("pool_w"), py::arg("pool_b"),

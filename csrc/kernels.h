@@ -191,6 +191,18 @@ int lk_bm25_partial(const long* term_ptr, long V, const int* post_doc, const uns
                     const float* kn, long N, const int* q_ptr, const int* q_term, const float* q_w, int nq,
                     int max_terms, int K, float* part_s, int* part_i, hipStream_t st);
 
+// mmr.hip
+// Greedy maximal-marginal-relevance selection (docs/mmr.md): per query K rounds over C candidates
+// (cand_id int32 / rel f32 [nq, C]; present iff 0 <= id < N and rel is not NaN), similarities between
+// the candidates' corpus rows in the kNN's form.  Outputs [nq, K]: position, chunk id, rel, mmr and
+// max_sim of each pick, (-1, -1, -inf, -inf, -inf) pads.  Refused: C outside 1..kLkMmrMaxCand (-1),
+// K outside 1..C (-2), D % 16 != 0 or D outside 16..1024 (-3), lam not in [0, 1] (-4), N >= 2^31 (-5).
+constexpr int kLkMmrMaxCand = 64;
+int lk_mmr_supported(long N, int D, int C, int K, float lam);
+int lk_mmr_select(const bf16_t* corpus, const float* cnorm, long N, int D, const int* cand_id, const float* rel,
+                  int nq, int C, float lam, int K, int* pos, int* ids, float* rel_out, float* mmr, float* max_sim,
+                  hipStream_t st);
+
 // pooling.hip
 int lk_pool_normalize(const bf16_t* hidden, long hs, const int* cu, int B, int H, int mode,
                       int normalize, void* out, long os, int out_bf16, hipStream_t st);

@@ -74,7 +74,10 @@ class RagAgentPipeline:
         if isinstance(qv, torch.Tensor) and qv.is_cuda:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        pending = self.index.search_vectors_async(qv, r.agent_topk)
+        if getattr(r, "agent_mmr_lambda", None) is None:
+            pending = self.index.search_vectors_async(qv, r.agent_topk)
+        else:  # opt-in: MMR selection on the kNN's device outputs (docs/mmr.md)
+            pending = self.index.search_vectors_async(qv, r.agent_topk, mmr=(r.agent_mmr_lambda, r.mmr_candidates))
         if ev1 is not None:
             ev1.record()
         return {"prompts": prompts, "pending": pending, "t": (t0, t1, time.perf_counter()), "ev": (ev0, ev1)}

@@ -4,7 +4,8 @@ and JSON contracts:
   GET  /health       -> {"status":"ok"}                                  (C2, :55)
   POST /rag/search   pure retrieval, topK default 5 clamp [1,10], best-score
                      0.20 floor, 260-char previews                        (C3, :62-100);
-                     optional "mode": dense | lexical | hybrid (docs/hybrid_search.md)
+                     optional "mode": dense | lexical | hybrid (docs/hybrid_search.md);
+                     optional "mmrLambda": MMR selection as the last stage (docs/mmr.md)
   POST /agent_rag    retrieve top-6 -> citations -> LLM tool call -> gated k8s
                      action -> {result, citations, note}                  (C4, :106-316)
 
@@ -26,7 +27,7 @@ from ..agent.json_extract import extract_json_object
 from ..agent.policy import select_citations
 from ..agent.prompts import RAG_AGENT_SYSTEM, json_prompt, rag_agent_input
 from ..agent.tools import dispatch_rag_tool
-from ..config import SEARCH_MODES, Config
+from ..config import SEARCH_MODES, Config, mmr_lambda_ok, validate_mmr
 from ..rag.chunking import is_blank, u16len, u16slice
 from ..utils import metrics as M
 from ..utils.logging import get_logger
@@ -52,6 +53,8 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
     app.state.reranker = reranker if r.rerank_model else None
     if r.search_mode not in SEARCH_MODES:
         raise ValueError(f"rag.search_mode must be one of {', '.join(SEARCH_MODES)} (got '{r.search_mode}')")
+    validate_mmr(r)
+    agent_mmr = None if r.agent_mmr_lambda is None else (r.agent_mmr_lambda, r.mmr_candidates)
     tracer = Tracer("rag_app")
     app.state.tracer = tracer
     if build_index and index is not None and len(index) == 0:
@@ -80,12 +83,13 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
 
     def knn_batch(qs):
         qa = np.stack([np.asarray(q, dtype=np.float32) for q in qs])
+        kw = {} if agent_mmr is None else {"mmr": agent_mmr}  # opt-in (docs/mmr.md)
         if knn_stream is None:
-            return index.search_vectors(qa, r.agent_topk)
+            return index.search_vectors(qa, r.agent_topk, **kw)
         import torch
 
         with torch.cuda.stream(knn_stream):
-            return index.search_vectors(qa, r.agent_topk)
+            return index.search_vectors(qa, r.agent_topk, **kw)
 
     knn_batcher = MicroBatcher(knn_batch, max_items=64)
 
@@ -98,7 +102,11 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
         if getattr(h, "fused_score", None) is not None:
             out = {"lexicalScore": h.lexical_score, "fusedScore": h.fused_score}
         rs = getattr(h, "rerank_score", None)
-        return out if rs is None else {**out, "rerankScore": rs}
+        if rs is not None:
+            out = {**out, "rerankScore": rs}
+        if getattr(h, "mmr_score", None) is not None:
+            out = {**out, "mmrScore": h.mmr_score, "maxSim": h.max_sim}
+        return out
 
     @app.post("/rag/search")
     async def rag_search(request: Request):
@@ -110,9 +118,16 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
         except BindError:
             return Response(status_code=400)
         mode = None
+        lam, lam_given = None, False
         for key, val in body.items():  # case-insensitive, like member()
             if key.lower() == "mode":
                 mode = val
+            elif key.lower() == "mmrlambda":
+                lam, lam_given = val, True
+        if not lam_given:
+            lam = r.mmr_lambda
+        elif lam is not None and not mmr_lambda_ok(lam):
+            return NetJSONResponse({"error": "mmrLambda must be a number between 0 and 1"}, status_code=400)
         if mode is None:
             mode = r.search_mode
         if not isinstance(mode, str) or mode not in SEARCH_MODES:
@@ -121,7 +136,13 @@ def create_rag_app(cfg: Optional[Config] = None, index=None, llm=None, k8s=None,
             return NetJSONResponse({"error": "Query vuota"}, status_code=400)
         k = r.search_default_topk if top_k is None else min(max(top_k, r.search_topk_min), r.search_topk_max)
         with tracer.span("rag.search", k=k):
-            if mode != "dense":  # opt-in first stage: BM25 alone, or fused with the cosine list
+            if lam is not None:  # opt-in last stage: MMR over the order of the stages before it
+                try:
+                    hits = await asyncio.to_thread(index.query, query, k, app.state.reranker, r.rerank_candidates, mode,
+                                                   float(lam), r.mmr_candidates)
+                except ValueError as e:  # a sharded corpus serves neither MMR nor the non-dense modes
+                    return NetJSONResponse({"error": f"{e}"}, status_code=400)
+            elif mode != "dense":  # opt-in first stage: BM25 alone, or fused with the cosine list
                 try:
                     hits = await asyncio.to_thread(index.query, query, k, app.state.reranker, r.rerank_candidates, mode)
                 except ValueError as e:  # a sharded corpus serves 'dense' only

@@ -54,6 +54,25 @@ class RagConfig:
     rrf_k: int = 60                                    # reciprocal-rank fusion: 1 / (rrf_k + rank)
     bm25_k1: float = 1.2
     bm25_b: float = 0.75
+    mmr_lambda: Optional[float] = None                 # /rag/search last stage: MMR in [0, 1] (off unless set)
+    mmr_candidates: int = 24                           # hits handed to the MMR selection (at most 64)
+    agent_mmr_lambda: Optional[float] = None           # /agent_rag retrieval: MMR in [0, 1] (off unless set)
+
+
+def mmr_lambda_ok(v) -> bool:
+    """A usable MMR lambda: a real number (no bool, no NaN) in [0, 1]."""
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 <= v <= 1.0
+
+
+def validate_mmr(r: "RagConfig"):
+    """The MMR settings, checked where an app starts (like ``search_mode``)."""
+    for name in ("mmr_lambda", "agent_mmr_lambda"):
+        v = getattr(r, name)
+        if v is not None and not mmr_lambda_ok(v):
+            raise ValueError(f"rag.{name} must be a number between 0 and 1, or unset (got {v!r})")
+    c = r.mmr_candidates
+    if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+        raise ValueError(f"rag.mmr_candidates must be a positive integer (got {c!r})")
 
 
 @dataclass

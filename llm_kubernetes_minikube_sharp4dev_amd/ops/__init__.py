@@ -22,7 +22,7 @@ __all__ = [
     "pool_normalize", "row_norms", "select_tokens", "repeat_penalty_", "sample", "linear", "linear_swiglu",
     "decode_splits", "rope_cos_sin", "argmax_key", "key_to_id", "tune_gemm", "tune_decode", "gemm", "linear_add_rmsnorm", "linear_rope_kv",
     "prefill_chain_ok", "linear_resid", "linear_qkv_fused", "linear_swiglu_scaled", "embed_rows", "scatter_ids",
-    "gather_rows", "token_logprobs", "rerank_head", "bm25_topk",
+    "gather_rows", "token_logprobs", "rerank_head", "bm25_topk", "mmr_select",
 ]
 
 rope_cos_sin = ref.rope_cos_sin
@@ -279,6 +279,21 @@ def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K: int):
         s, i = lib().bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, int(K))
         return s, i
     return ref.bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K)
+
+
+def mmr_select(corpus, cnorm, cand_id, rel, lam: float, K: int):
+    """Maximal-marginal-relevance selection over candidate lists (docs/mmr.md): per query K greedy
+    rounds of ``mmr_i = lam * rel_i - (1 - lam) * max_sim_i`` over the C candidates ``cand_id`` int32 /
+    ``rel`` f32 [nq, C] (present iff ``0 <= id < N`` and ``rel`` is not NaN), similarities between the
+    candidates' rows of ``corpus`` bf16 [N, D] in the kNN's form with ``cnorm`` f32 [N] -> (pos int32,
+    ids int32, rel f32, mmr f32, max_sim f32), each [nq, K], ties to the lower position, pads
+    (-1, -1, -inf, -inf, -inf).  C outside 1..64, K outside 1..C, D % 16 != 0 or outside 16..1024, a
+    ``lam`` outside [0, 1], mismatched shapes or other dtypes raise before anything runs."""
+    ref.mmr_check(corpus, cnorm, cand_id, rel, lam, K)
+    if use_hip(corpus):
+        return tuple(lib().mmr_select(corpus.contiguous(), cnorm.contiguous(), cand_id.contiguous(),
+                                      rel.contiguous(), float(lam), int(K)))
+    return ref.mmr_select(corpus, cnorm, cand_id, rel, lam, K)
 
 
 def pool_normalize(hidden, cu, mode: int, normalize: bool = True, out=None):

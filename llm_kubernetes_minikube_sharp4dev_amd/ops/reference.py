@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -300,6 +301,84 @@ def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K):
         out_s[q, :len(order)] = sc[order]
         out_i[q, :len(order)] = order
     return torch.from_numpy(out_s), torch.from_numpy(out_i)
+
+
+MMR_MAX_CAND = 64     # csrc/kernels.h kLkMmrMaxCand
+
+
+def mmr_check(corpus, cnorm, cand_id, rel, lam, K):
+    """The limits of ``mmr_select`` (csrc/mmr.hip), each refused by the argument's name."""
+    if corpus.dim() != 2 or corpus.dtype != torch.bfloat16:
+        raise ValueError("mmr_select: corpus must be bfloat16 [N, D]")
+    N, D = corpus.shape
+    if cnorm.dtype != torch.float32 or tuple(cnorm.shape) != (N,):
+        raise ValueError("mmr_select: cnorm must be float32 [N]")
+    if cand_id.dtype != torch.int32:
+        raise ValueError("mmr_select: cand_id must be int32")
+    if rel.dtype != torch.float32:
+        raise ValueError("mmr_select: rel must be float32")
+    if cand_id.dim() != 2 or cand_id.shape != rel.shape:
+        raise ValueError("mmr_select: cand_id and rel must have the same shape [nq, C]")
+    C = cand_id.shape[1]
+    if not 1 <= C <= MMR_MAX_CAND:
+        raise ValueError(f"mmr_select: C (the width of cand_id) must be in [1, {MMR_MAX_CAND}] (got {C})")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= C:
+        raise ValueError(f"mmr_select: K must be an integer in [1, C = {C}] (got {K!r})")
+    if D % 16 or not 16 <= D <= 1024:
+        raise ValueError(f"mmr_select: D must be a multiple of 16 in [16, 1024] (got {D})")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.floating, np.integer)) or not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"mmr_select: lam must be a finite number in [0, 1] (got {lam!r})")
+    if N >= 1 << 31:
+        raise ValueError(f"mmr_select: N must be below 2^31 (got {N})")
+
+
+def mmr_select(corpus, cnorm, cand_id, rel, lam, K):
+    """fp32, in the kernel's operation order (csrc/mmr.hip, docs/mmr.md): candidate i of a row is
+    present iff ``0 <= cand_id[i] < N`` and ``rel[i]`` is not NaN; ``sim(i, j) = dot(c_i, c_j) /
+    (cnorm[id_i] * cnorm[id_j] + 1e-9)`` with a plain fp32 matmul of the bf16 rows; K greedy rounds of
+    ``mmr_i = lam * rel_i - (1 - lam) * m_i`` -- the two products and the difference each rounded to
+    f32, ``1 - lam`` formed in f32 -- where ``m_i`` is 0 in round 0 and afterwards the largest
+    similarity to a pick (assigned from the first pick); the pick is the present, not yet selected
+    candidate with the largest mmr, ties to the lower position; a NaN mmr is not picked.
+    -> (pos int32, ids int32, rel f32, mmr f32, max_sim f32), each [nq, K]; pads (-1, -1, -inf, -inf, -inf)."""
+    mmr_check(corpus, cnorm, cand_id, rel, lam, K)
+    K = int(K)
+    X = corpus.float().cpu().numpy()
+    cn = cnorm.cpu().numpy().astype(np.float32)
+    cid = cand_id.cpu().numpy()
+    rl = rel.cpu().numpy().astype(np.float32)
+    N = X.shape[0]
+    nq, C = cid.shape
+    lam32 = np.float32(lam)
+    oml = np.float32(1.0) - lam32
+    o_pos = np.full((nq, K), -1, np.int32)
+    o_id = np.full((nq, K), -1, np.int32)
+    o_rel = np.full((nq, K), -np.inf, np.float32)
+    o_mmr = np.full((nq, K), -np.inf, np.float32)
+    o_sim = np.full((nq, K), -np.inf, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(nq):
+            inside = (cid[q] >= 0) & (cid[q] < N)
+            avail = inside & ~np.isnan(rl[q])
+            if not avail.any():
+                continue
+            cl = np.where(inside, cid[q], 0)
+            rows = X[cl]
+            c = np.where(inside, cn[cl], np.float32(1.0)).astype(np.float32)
+            den = (c[:, None] * c[None, :]).astype(np.float32) + np.float32(1e-9)
+            S = ((rows @ rows.T).astype(np.float32) / den).astype(np.float32)
+            lr = (lam32 * rl[q]).astype(np.float32)
+            m = np.zeros(C, np.float32)
+            for r in range(K):
+                v = (lr - (oml * m).astype(np.float32)).astype(np.float32)
+                ok = avail & ~np.isnan(v)
+                if not ok.any():
+                    break
+                p = int(np.lexsort((np.arange(C), -np.where(ok, v, -np.inf), ~ok))[0])
+                o_pos[q, r], o_id[q, r], o_rel[q, r], o_mmr[q, r], o_sim[q, r] = p, cid[q, p], rl[q, p], v[p], m[p]
+                avail[p] = False
+                m = S[:, p].copy() if r == 0 else np.where(S[:, p] > m, S[:, p], m)
+    return tuple(torch.from_numpy(a) for a in (o_pos, o_id, o_rel, o_mmr, o_sim))
 
 
 def pool_normalize(hidden, cu, mode, normalize):

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..config import SEARCH_MODES
+from ..config import SEARCH_MODES, mmr_lambda_ok
 from ..utils import metrics as M
 from ..utils.logging import get_logger
 from ..utils.tracing import Tracer
@@ -62,6 +62,8 @@ class RagHit:                        # record RagHit(Id, Source, Text, double Sc
     rerank_score: Optional[float] = None  # set by RagIndex.query(..., reranker=...)
     lexical_score: Optional[float] = None  # BM25, modes 'lexical' / 'hybrid'; None: not in the lexical list
     fused_score: Optional[float] = None    # reciprocal-rank fusion score, modes 'lexical' / 'hybrid'
+    mmr_score: Optional[float] = None      # MMR value at the time of the pick (query(..., mmr_lambda=...))
+    max_sim: Optional[float] = None        # largest similarity to an earlier pick (0 for the first)
 
 
 def cosine_exact(a: np.ndarray, b: np.ndarray) -> float:
@@ -84,6 +86,42 @@ def rrf_fuse(lists: Sequence[Sequence[int]], rrf_k: int = 60) -> dict[int, float
         for rank, d in enumerate(ranked, 1):
             fused[d] = fused.get(d, 0.0) + 1.0 / (rrf_k + rank)
     return fused
+
+
+MMR_MAX_CANDIDATES = 64  # csrc/kernels.h kLkMmrMaxCand
+_SHARDED_MMR = "MMR is not supported with a sharded (tensor-parallel) corpus: leave mmr_lambda unset"
+
+
+def _check_mmr_lambda(lam) -> float:
+    if not mmr_lambda_ok(lam):
+        raise ValueError(f"mmr_lambda must be a number between 0 and 1 (got {lam!r})")
+    return float(lam)
+
+
+def mmr_select_f64(rows: np.ndarray, rel: Sequence[float], lam: float, K: int) -> list[tuple[int, float, float]]:
+    """Greedy MMR (docs/mmr.md) over the candidates ``rows`` f32 [C, D] in float64, the exact backend's
+    counterpart of ``ops.mmr_select``: similarities in the arithmetic of :func:`cosine_exact` (f32
+    products, f64 sums), ``mmr_i = lam * rel_i - (1 - lam) * m_i`` with ``m_i`` 0 in the first round
+    and afterwards the largest similarity to a pick (assigned from the first pick), ties to the lower
+    position; a NaN ``rel`` is absent.  -> at most K picks [(position, mmr, max_sim)]."""
+    rows = np.asarray(rows, dtype=np.float32)
+    C = len(rows)
+    nrm = np.sqrt((rows * rows).astype(np.float64).sum(1)) if C else np.zeros(0)
+    relv = np.asarray(rel, dtype=np.float64)
+    avail = ~np.isnan(relv)
+    m = np.zeros(C)
+    out: list[tuple[int, float, float]] = []
+    for r in range(min(K, C)):
+        v = lam * relv - (1.0 - lam) * m
+        ok = avail & ~np.isnan(v)
+        if not ok.any():
+            break
+        p = min((i for i in range(C) if ok[i]), key=lambda i: (-v[i], i))
+        out.append((p, float(v[p]), float(m[p])))
+        avail[p] = False
+        sim = (rows * rows[p][None, :]).astype(np.float64).sum(1) / (nrm * nrm[p] + 1e-9)
+        m = sim if r == 0 else np.maximum(m, sim)
+    return out
 
 
 def enumerate_files(folder: str) -> list[str]:
@@ -202,16 +240,25 @@ class RagIndex:
         if search_fn is not None:
             self._gpu = None
 
-    def search_vectors_async(self, q: np.ndarray | torch.Tensor, top_k: int) -> "PendingSearch":
+    def search_vectors_async(self, q: np.ndarray | torch.Tensor, top_k: int,
+                             mmr: Optional[tuple[float, int]] = None) -> "PendingSearch":
         """Launch a batched search without blocking the host: on the GPU the kNN kernel and
         one non-blocking copy of its (scores, ids) into pinned memory are enqueued on the
         current stream behind an event; :meth:`PendingSearch.result` waits for that event
         only (an engine thread collects it after its next step, when it has long completed).
-        Elsewhere the search runs synchronously."""
+        Elsewhere the search runs synchronously.
+
+        ``mmr = (lam, C)``: the kNN returns ``min(64, max(top_k, C))`` hits and ``ops.mmr_select``
+        (docs/mmr.md) picks ``top_k`` of them on the kNN's device outputs, on the same stream; the
+        rows keep their type, [(chunk_index, cosine)], now in MMR order."""
         k = max(1, top_k)
         n = len(self.chunks)
+        if mmr is not None:
+            lam, pool = _check_mmr_lambda(mmr[0]), min(MMR_MAX_CANDIDATES, max(k, int(mmr[1])))
+            if getattr(self, "_sharded", None) is not None:
+                raise ValueError(_SHARDED_MMR)
         if n == 0 or not self._use_gpu():
-            return PendingSearch(done=self.search_vectors(q, top_k) if n else [[] for _ in range(len(q))])
+            return PendingSearch(done=self.search_vectors(q, top_k, mmr) if n else [[] for _ in range(len(q))])
         qt = torch.as_tensor(q)
         sharded = getattr(self, "_sharded", None)
         if sharded is not None:
@@ -226,7 +273,11 @@ class RagIndex:
             qt = (qt.to(torch.bfloat16).to(self.device) if qt.device.type == "cpu"
                   else qt.to(self.device, torch.bfloat16)).reshape(-1, corpus.shape[1]).contiguous()
             qn = ops.row_norms(qt) if qt.is_cuda else qt.float().norm(dim=-1)
-            s, i = ops.knn_topk(corpus, norms, qt, qn, min(k, 64))
+            if mmr is None:
+                s, i = ops.knn_topk(corpus, norms, qt, qn, min(k, 64))
+            else:
+                cs, ci = ops.knn_topk(corpus, norms, qt, qn, pool)
+                _, i, s, _, _ = ops.mmr_select(corpus, norms, ci, cs, lam, min(k, pool))
         if not s.is_cuda:
             return PendingSearch(done=_rows(s.tolist(), i.tolist(), min(k, n)))
         hs = torch.empty(s.shape, dtype=s.dtype, pin_memory=True)
@@ -237,14 +288,20 @@ class RagIndex:
         ev.record()
         return PendingSearch(host=(hs, hi, min(k, n)), event=ev)
 
-    def search_vectors(self, q: np.ndarray | torch.Tensor, top_k: int) -> list[list[tuple[int, float]]]:
-        """Batched: q [nq, D] -> per query [(chunk_index, score)] (stable order)."""
+    def search_vectors(self, q: np.ndarray | torch.Tensor, top_k: int,
+                       mmr: Optional[tuple[float, int]] = None) -> list[list[tuple[int, float]]]:
+        """Batched: q [nq, D] -> per query [(chunk_index, score)] (stable order); with ``mmr =
+        (lam, C)`` the MMR selection of ``top_k`` among the best ``min(64, max(top_k, C))``."""
         k = max(1, top_k)
         n = len(self.chunks)
+        if mmr is not None:
+            lam, pool = _check_mmr_lambda(mmr[0]), min(MMR_MAX_CANDIDATES, max(k, int(mmr[1])))
+            if getattr(self, "_sharded", None) is not None:
+                raise ValueError(_SHARDED_MMR)
         if n == 0:
             return [[] for _ in range(len(q))]
         if self._use_gpu():
-            return self.search_vectors_async(q, top_k).result()
+            return self.search_vectors_async(q, top_k, mmr).result()
         mat = self.matrix()
         qa = np.asarray(q.float().cpu().numpy() if isinstance(q, torch.Tensor) else q, dtype=np.float32)
         if qa.ndim == 1:
@@ -258,7 +315,11 @@ class RagIndex:
                 na = float(np.sum((qv * qv).astype(np.float64)))
                 nb = (mat * mat).astype(np.float64).sum(1)
                 scores = prod / (np.sqrt(na) * np.sqrt(nb) + 1e-9)
-            order = np.argsort(-scores, kind="stable")[: min(k, n)]
+            if mmr is None:
+                order = np.argsort(-scores, kind="stable")[: min(k, n)]
+            else:
+                cand = np.argsort(-scores, kind="stable")[: min(pool, n)]
+                order = [cand[p] for p, _, _ in mmr_select_f64(mat[cand], scores[cand], lam, k)]
             out.append([(int(j), float(scores[j])) for j in order])
         return out
 
@@ -309,7 +370,7 @@ class RagIndex:
         nb = (mat * mat).astype(np.float64).sum(1)
         return (prod / (np.sqrt(na) * np.sqrt(nb) + 1e-9)).tolist()
 
-    def _query_fused(self, query: str, k: int, take: int, mode: str) -> list[RagHit]:
+    def _query_fused(self, query: str, k: int, take: int, mode: str, order_out: Optional[list] = None) -> list[RagHit]:
         """The best ``take`` chunks of the lexical order ('lexical') or of the reciprocal-rank fusion
         of the lexical and the cosine list ('hybrid'): fused(d) = sum over the lists holding d of
         1 / (rrf_k + rank), rank 1-based, sorted by fused descending, ties by lower chunk index."""
@@ -330,12 +391,68 @@ class RagIndex:
             lists.append([d for d, _ in dense])
         fused = rrf_fuse(lists, self.rrf_k)
         order = sorted(fused, key=lambda d: (-fused[d], d))[:take]
+        if order_out is not None:  # the hits' chunk indices, for a later stage that needs the rows
+            order_out.extend(order)
         missing = [d for d in order if d not in cos]
         cos.update(zip(missing, self.cosines(np.asarray(qv)[0], missing)))
         return [RagHit(self.chunks[d].id, self.chunks[d].source, self.chunks[d].text, float(cos[d]),
                        lexical_score=bm25.get(d), fused_score=fused[d]) for d in order]
 
-    def query(self, query: str, top_k: int = 5, reranker=None, candidates: int = 24, mode: str = "dense") -> list[RagHit]:
+    def _query_mmr(self, query: str, top_k: int, reranker, candidates: int, mode: str, lam: float,
+                   mmr_candidates: int) -> list[RagHit]:
+        """:meth:`query` with MMR as the last stage (docs/mmr.md): the earlier stages produce their
+        order over a pool of ``min(64, max(top_k, mmr_candidates))`` hits, whose relevance is the
+        cosine ('dense'), the rerank score (with a reranker) or ``fused_score * (rrf_k + 1) /
+        n_lists`` ('hybrid' / 'lexical'); ``top_k`` of them are picked greedily."""
+        if mode not in SEARCH_MODES:
+            raise ValueError(f"mode must be one of {', '.join(SEARCH_MODES)} (got {mode!r})")
+        lam = _check_mmr_lambda(lam)
+        if getattr(self, "_sharded", None) is not None:
+            raise ValueError(_SHARDED_MMR)
+        k = max(1, top_k)
+        pool = min(MMR_MAX_CANDIDATES, max(k, int(mmr_candidates)))
+        take = pool if reranker is None else min(MMR_MAX_CANDIDATES, max(k, int(candidates), int(mmr_candidates)))
+        idx: list[int] = []
+        if mode != "dense":
+            hits = self._query_fused(query, k, take, mode, idx)
+            scale = (self.rrf_k + 1) / (2 if mode == "hybrid" else 1)
+            rel = [h.fused_score * scale for h in hits]
+        else:
+            res = self.search_vectors(self.embedder.embed([query]), take)[0]
+            idx = [j for j, _ in res]
+            hits = self.hits(res)
+            rel = [h.score for h in hits]
+        if not hits:
+            return hits
+        if reranker is not None:
+            rs = [float(s) for s in reranker.score(query, [h.text for h in hits])]
+            if len(rs) != len(hits):
+                raise ValueError(f"reranker returned {len(rs)} scores for {len(hits)} documents")
+            order = sorted(range(len(hits)), key=lambda i: (-rs[i], i))[:pool]
+            for i in order:
+                hits[i].rerank_score = rs[i]
+            hits, idx, rel = [hits[i] for i in order], [idx[i] for i in order], [rs[i] for i in order]
+        else:
+            hits, idx, rel = hits[:pool], idx[:pool], rel[:pool]
+        kk = min(k, len(hits))
+        with _tracer.span("rag.mmr", lam=lam, candidates=len(hits), k=kk):
+            if self._use_gpu():
+                corpus, norms = self.gpu_tensors()
+                dev = corpus.device
+                cid = torch.tensor([idx], dtype=torch.int32, device=dev)
+                rl = torch.tensor([rel], dtype=torch.float32, device=dev)
+                pos, _, _, mm, ms = ops.mmr_select(corpus, norms, cid, rl, lam, kk)
+                picks = [(p, v, s) for p, v, s in zip(pos[0].tolist(), mm[0].tolist(), ms[0].tolist()) if p >= 0]
+            else:
+                picks = mmr_select_f64(self.matrix()[idx], rel, lam, kk)
+        out = []
+        for p, v, s in picks:
+            hits[p].mmr_score, hits[p].max_sim = float(v), float(s)
+            out.append(hits[p])
+        return out
+
+    def query(self, query: str, top_k: int = 5, reranker=None, candidates: int = 24, mode: str = "dense",
+              mmr_lambda: Optional[float] = None, mmr_candidates: int = 24) -> list[RagHit]:
         """Top ``top_k`` hits by cosine.  With a ``reranker`` (``score(query, docs) -> floats``, see
         :mod:`.reranker`): ``max(top_k, candidates)`` cosine hits are scored by it and the best
         ``top_k`` come back in rerank order (ties by cosine rank); every hit keeps its cosine as
@@ -345,7 +462,13 @@ class RagIndex:
         the cosine list, ``min(64, max(top_k, hybrid_candidates))`` hits from each
         (docs/hybrid_search.md); the hits carry ``lexical_score`` and ``fused_score``, ``score`` stays
         the cosine, and a reranker scores the best ``max(top_k, candidates)`` of that order.  'dense'
-        (the default) is the cosine scan alone."""
+        (the default) is the cosine scan alone.
+
+        ``mmr_lambda`` in [0, 1] adds maximal-marginal-relevance selection as the last stage
+        (docs/mmr.md) over the first ``min(64, max(top_k, mmr_candidates))`` hits of that order; the
+        hits then carry ``mmr_score`` and ``max_sim``.  None (the default) is the path without it."""
+        if mmr_lambda is not None:
+            return self._query_mmr(query, top_k, reranker, candidates, mode, mmr_lambda, mmr_candidates)
         if mode not in SEARCH_MODES:
             raise ValueError(f"mode must be one of {', '.join(SEARCH_MODES)} (got {mode!r})")
         if mode != "dense":
