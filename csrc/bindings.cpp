@@ -690,6 +690,23 @@ at::Tensor flash_prefill(const at::Tensor& q, const at::Tensor& k, const at::Ten
   return out;
 }
 
+// the result of a top-k over nothing (no rows or no queries): (-inf, -1) pads, [nq, K]
+std::vector<at::Tensor> topk_pads(long nq, long K, const at::TensorOptions& fo, const at::TensorOptions& io) {
+  return {at::full({nq, K}, -INFINITY, fo), at::full({nq, K}, -1, io)};
+}
+
+// pass 2 of every top-k: partial lists ps / pi [nq, n, kk] -> the K best per query, [nq, K]; the
+// merge kernel writes every one of the K slots of every query (-inf / -1 pads)
+std::vector<at::Tensor> merge_partials(const at::Tensor& ps, const at::Tensor& pi, long K, const char* name) {
+  const int nq = ps.size(0);
+  at::Tensor out_s = at::empty({nq, K}, ps.options());
+  at::Tensor out_i = at::empty({nq, K}, pi.options());
+  int rc = lk_knn_merge(ps.data_ptr<float>(), pi.data_ptr<int>(), nq, (int)(ps.size(1) * ps.size(2)), (int)K,
+                        out_s.data_ptr<float>(), out_i.data_ptr<int>(), cur_stream());
+  CHECK_RC(rc, name);
+  return {out_s, out_i};
+}
+
 std::vector<at::Tensor> knn_topk(const at::Tensor& corpus, const at::Tensor& cnorm, const at::Tensor& queries,
                                  const at::Tensor& qnorm, int64_t K, bool force_fused) {
   CHECK_CUDA(corpus); CHECK_BF16(corpus); CHECK_CONTIG(corpus); CHECK_F32(cnorm); CHECK_CONTIG(cnorm);
@@ -702,10 +719,7 @@ std::vector<at::Tensor> knn_topk(const at::Tensor& corpus, const at::Tensor& cno
   auto fo = corpus.options().dtype(at::kFloat);
   auto io = corpus.options().dtype(at::kInt);
   const int kk = (int)std::min<long>(K, std::max<long>(N, 1));
-  // the merge kernel writes every one of the K slots of every query (-inf / -1 pads)
-  if (N == 0 || nq == 0) return {at::full({nq, (long)K}, -INFINITY, fo), at::full({nq, (long)K}, -1, io)};
-  at::Tensor out_s = at::empty({nq, (long)K}, fo);
-  at::Tensor out_i = at::empty({nq, (long)K}, io);
+  if (N == 0 || nq == 0) return topk_pads(nq, K, fo, io);
   if (D % 64 == 0 && nq <= 256 && !force_fused) {
     // corpus streamed once by the LDS-DMA weight-streaming GEMM (dots in f32), then a
     // normalise + chunked top-k pass and the shared merge
@@ -718,10 +732,7 @@ std::vector<at::Tensor> knn_topk(const at::Tensor& corpus, const at::Tensor& cno
     rc = lk_knn_score_topk(scores.data_ptr<float>(), N, cnorm.data_ptr<float>(), qnorm.data_ptr<float>(), N, nq, kk,
                            ps.data_ptr<float>(), pi.data_ptr<int>(), cur_stream());
     CHECK_RC(rc, "knn score_topk");
-    rc = lk_knn_merge(ps.data_ptr<float>(), pi.data_ptr<int>(), nq, nc * kk, (int)K, out_s.data_ptr<float>(),
-                      out_i.data_ptr<int>(), cur_stream());
-    CHECK_RC(rc, "knn_merge");
-    return {out_s, out_i};
+    return merge_partials(ps, pi, K, "knn_merge");
   }
   const int nb = lk_knn_nblocks(N);
   at::Tensor ps = at::empty({nq, nb, kk}, fo);
@@ -729,22 +740,13 @@ std::vector<at::Tensor> knn_topk(const at::Tensor& corpus, const at::Tensor& cno
   int rc = lk_knn_partial(bp(corpus), cnorm.data_ptr<float>(), N, D, bp(queries), qnorm.data_ptr<float>(), nq, kk,
                           ps.data_ptr<float>(), pi.data_ptr<int>(), cur_stream());
   CHECK_RC(rc, "knn_partial");
-  rc = lk_knn_merge(ps.data_ptr<float>(), pi.data_ptr<int>(), nq, nb * kk, (int)K, out_s.data_ptr<float>(),
-                    out_i.data_ptr<int>(), cur_stream());
-  CHECK_RC(rc, "knn_merge");
-  return {out_s, out_i};
+  return merge_partials(ps, pi, K, "knn_merge");
 }
 
 std::vector<at::Tensor> knn_merge(const at::Tensor& cand_s, const at::Tensor& cand_i, int64_t K) {
   CHECK_CUDA(cand_s); CHECK_F32(cand_s); CHECK_I32(cand_i); CHECK_CONTIG(cand_s); CHECK_CONTIG(cand_i);
   TORCH_CHECK(cand_s.dim() == 2 && cand_s.sizes() == cand_i.sizes(), "candidates [nq, ncand]");
-  const int nq = cand_s.size(0), nc = cand_s.size(1);
-  at::Tensor out_s = at::empty({nq, K}, cand_s.options());
-  at::Tensor out_i = at::empty({nq, K}, cand_i.options());
-  int rc = lk_knn_merge(cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), nq, nc, (int)K, out_s.data_ptr<float>(),
-                        out_i.data_ptr<int>(), cur_stream());
-  CHECK_RC(rc, "knn_merge");
-  return {out_s, out_i};
+  return merge_partials(cand_s.unsqueeze(1), cand_i.unsqueeze(1), K, "knn_merge");
 }
 
 // BM25 top-K over a CSR-by-term inverted index (csrc/bm25.hip + the kNN merge): -> (scores f32
@@ -779,22 +781,17 @@ std::vector<at::Tensor> bm25_topk(const at::Tensor& term_ptr, const at::Tensor& 
   CHECK_RC(lk_bm25_supported(N, nq, max_terms, (int)std::min<int64_t>(std::max<int64_t>(K, -1), 1 << 20)), "bm25_topk");
   auto fo = kn.options().dtype(at::kFloat);
   auto io = kn.options().dtype(at::kInt);
-  if (N == 0 || nq == 0) return {at::full({nq, (long)K}, -INFINITY, fo), at::full({nq, (long)K}, -1, io)};
+  if (N == 0 || nq == 0) return topk_pads(nq, K, fo, io);
   const at::Tensor qd = q_ptr.is_cuda() ? q_ptr : q_ptr.to(kn.device());
   const int nc = lk_bm25_chunks(N);
   at::Tensor ps = at::empty({nq, nc, (long)K}, fo);
   at::Tensor pi = at::empty({nq, nc, (long)K}, io);
-  at::Tensor out_s = at::empty({nq, (long)K}, fo);
-  at::Tensor out_i = at::empty({nq, (long)K}, io);
   int rc = lk_bm25_partial(reinterpret_cast<const long*>(term_ptr.data_ptr<int64_t>()), V, ip(post_doc),
                            post_tf.data_ptr<uint8_t>(), nnz, kn.data_ptr<float>(), N, ip(qd), ip(q_term),
                            q_w.data_ptr<float>(), nq, max_terms, (int)K, ps.data_ptr<float>(), pi.data_ptr<int>(),
                            cur_stream());
   CHECK_RC(rc, "bm25_topk");
-  rc = lk_knn_merge(ps.data_ptr<float>(), pi.data_ptr<int>(), nq, nc * (int)K, (int)K, out_s.data_ptr<float>(),
-                    out_i.data_ptr<int>(), cur_stream());
-  CHECK_RC(rc, "bm25 merge");
-  return {out_s, out_i};
+  return merge_partials(ps, pi, K, "bm25 merge");
 }
 
 // MMR selection over candidate lists (csrc/mmr.hip): -> (pos int32, ids int32, rel f32, mmr f32,

@@ -15,15 +15,15 @@
 // duplicate-free) and two terms never run concurrently: no atomics, one fixed summation order per
 // document, the same bits on every run.  The quotient, the product and the add are each rounded
 // once (the product is kept out of an FMA), so the kernel computes what the fp32 reference
-// computes.  The chunk's top-k comes out by k rounds of block-wide argmax over the slots with
-// score > 0, stopping at the first round that finds none.
+// computes.  The chunk's top-k comes out of the block-wide rounds of topk.h (topk_rounds) over
+// the slots with score > 0; every other slot enters them as -inf.
 // Pass 2: lk_knn_merge (knn.hip) over nchunks * K candidates per query; it skips id < 0.
 //
 // Nothing the device reads is trusted to index memory: term ids outside [0, V) are empty terms,
 // posting ranges are clamped to [0, nnz], a query's terms to kLkBm25MaxTerms, and a posting whose
 // document falls outside the chunk is ignored.
-#include "common.h"
 #include "kernels.h"
+#include "topk.h"
 
 namespace {
 
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void bm25_partial_kernel(
   __shared__ float w_s[MAXT];
   __shared__ float rs[4];
   __shared__ int ri[4];
-  const int q = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
   const long base = (long)c * C;
   const int q0 = q_ptr[q];
   int nt = q_ptr[q + 1] - q0;
@@ -118,47 +118,7 @@ __global__ __launch_bounds__(256) void bm25_partial_kernel(
     const float s = score[j * 256 + tid];
     v[j] = (s > 0.f && base + j * 256 + tid < N) ? s : -INFINITY;
   }
-  for (int kk = 0; kk < K; ++kk) {
-    float bs = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int idx = (int)(base + j * 256 + tid);
-      if (better(v[j], idx, bs, bi)) {
-        bs = v[j];
-        bi = idx;
-      }
-    }
-    wave_argmax(bs, bi);
-    if (lane == 0) {
-      rs[w] = bs;
-      ri[w] = bi;
-    }
-    __syncthreads();
-    float fs = rs[0];
-    int fi = ri[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-      if (better(rs[j], ri[j], fs, fi)) {
-        fs = rs[j];
-        fi = ri[j];
-      }
-    if (fs == -INFINITY) {  // no positive slot left (every lane sees the same fs): the rest are pads
-      for (int r = kk + tid; r < K; r += 256) {
-        ps[r] = -INFINITY;
-        pi[r] = -1;
-      }
-      return;
-    }
-    if (tid == 0) {
-      ps[kk] = fs;
-      pi[kk] = fi;
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-      if ((int)(base + j * 256 + tid) == fi) v[j] = -INFINITY;
-    __syncthreads();
-  }
+  topk_rounds(v, base, K, ps, pi, rs, ri);
 }
 
 }  // namespace

@@ -49,24 +49,6 @@ LK_DEVICE float wave_max(float v) {
   return v;
 }
 
-// (score desc, index asc) ordering, indices compared as unsigned, and its 64-lane argmax: the top-k
-// rounds of knn.hip and bm25.hip
-LK_DEVICE bool better(float s1, int i1, float s2, int i2) {
-  return s1 > s2 || (s1 == s2 && (unsigned)i1 < (unsigned)i2);
-}
-
-LK_DEVICE void wave_argmax(float& s, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s2 = __shfl_xor(s, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    if (better(s2, i2, s, i)) {
-      s = s2;
-      i = i2;
-    }
-  }
-}
-
 // block-wide sum for blockDim.x = NW*64; `red` must hold NW floats.
 template <int NW>
 LK_DEVICE float block_sum(float v, float* red) {

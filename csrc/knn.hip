@@ -11,12 +11,12 @@
 // permuted so every lane streams 64 contiguous bytes of its corpus row per group of
 // 4 k-steps (the reduction order of a dot product is free).  Scores are staged in
 // LDS and each wave extracts the block-local top-k of 8 queries by k rounds of
-// wave-wide (score, index) argmax.
+// wave-wide argmax: the rounds of topk.h, where the tie rule and the pads are defined.
 // Pass 2 (lk_knn_merge): one workgroup per query merges nblocks*k candidates with
 // the same tie rule.  Sharded (multi-GPU) search reuses pass 2 on all-gathered
 // candidates.
-#include "common.h"
 #include "kernels.h"
+#include "topk.h"
 
 namespace {
 
@@ -97,9 +97,13 @@ __global__ __launch_bounds__(256) void knn_partial_kernel(
     for (int j = 0; j < ROWS / 64; ++j) v[j] = sc[qq][lane + 64 * j];
     float* ps = part_s + ((long)(qbase + qq) * nblocks + blockIdx.x) * K;
     int* pi = part_i + ((long)(qbase + qq) * nblocks + blockIdx.x) * K;
+    // The rounds of topk.h (topk_rounds) written out for a wave, all K of them: with the shared
+    // routine this route measured 1 % slower, beyond the run-to-run spread (profiles/topk_rounds.md).
+    // The compiler cannot see that the early stop is the same in every lane and builds a divergent
+    // loop around the rounds.  The output is the same: a round won with -inf writes the pad.
     for (int kk = 0; kk < K; ++kk) {
       float bs = -INFINITY;
-      int bi = 0x7fffffff;
+      int bi = kNoCand;
 #pragma unroll
       for (int j = 0; j < ROWS / 64; ++j) {
         const int idx = (int)(row0 + lane + 64 * j);
@@ -122,8 +126,8 @@ __global__ __launch_bounds__(256) void knn_partial_kernel(
 
 // Top-k over precomputed dot products (scores [nq, ld] from the weight-streaming GEMM,
 // csrc/skinny_gemm.hip lk_ws_scores_f32): one workgroup per (chunk of 4096 rows, query)
-// normalises dot / (|q| |c| + 1e-9) and extracts the chunk's top-k (score desc, index
-// asc) by k rounds of block-wide argmax.
+// normalises dot / (|q| |c| + 1e-9) and extracts the chunk's top-k with the block-wide
+// rounds of topk.h (topk_rounds).
 constexpr int SCH = 4096;
 
 __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict__ scores, long ld,
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
                                                          int nchunks) {
   __shared__ float rs[4];
   __shared__ int ri[4];
-  const int q = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
   constexpr int PER = SCH / 256;
   const long base = (long)c * SCH;
   const float qn = qnorm[q];
@@ -145,40 +149,7 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
   }
   float* ps = part_s + ((long)q * nchunks + c) * K;
   int* pi = part_i + ((long)q * nchunks + c) * K;
-  for (int kk = 0; kk < K; ++kk) {
-    float bs = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int idx = (int)(base + j * 256 + tid);
-      if (better(v[j], idx, bs, bi)) {
-        bs = v[j];
-        bi = idx;
-      }
-    }
-    wave_argmax(bs, bi);
-    if (lane == 0) {
-      rs[w] = bs;
-      ri[w] = bi;
-    }
-    __syncthreads();
-    float fs = rs[0];
-    int fi = ri[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-      if (better(rs[j], ri[j], fs, fi)) {
-        fs = rs[j];
-        fi = ri[j];
-      }
-    if (tid == 0) {
-      ps[kk] = fs;
-      pi[kk] = fs == -INFINITY ? -1 : fi;
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-      if ((int)(base + j * 256 + tid) == fi) v[j] = -INFINITY;
-    __syncthreads();
-  }
+  topk_rounds(v, base, K, ps, pi, rs, ri);
 }
 
 // merge: one workgroup per query over `ncand` (score, idx) candidates
@@ -188,8 +159,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
                                                         int* __restrict__ out_i) {
   __shared__ float rs[4];
   __shared__ int ri[4];
-  __shared__ int last;
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = blockIdx.x, tid = threadIdx.x;
   const float* s = cs + (long)q * ncand;
   const int* ix = ci + (long)q * ncand;
   float prev_s = INFINITY;
@@ -197,7 +167,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
   for (int kk = 0; kk < K; ++kk) {
     // best candidate strictly "worse" than the previous winner
     float bs = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = kNoCand;
     for (int c = tid; c < ncand; c += 256) {
       const float v = s[c];
       const int id = ix[c];
@@ -208,31 +178,15 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
         bi = id;
       }
     }
-    wave_argmax(bs, bi);
-    if (lane == 0) {
-      rs[w] = bs;
-      ri[w] = bi;
-    }
-    __syncthreads();
+    block_argmax(bs, bi, rs, ri);
     if (tid == 0) {
-      float fs = rs[0];
-      int fi = ri[0];
-      for (int j = 1; j < 4; ++j)
-        if (better(rs[j], ri[j], fs, fi)) {
-          fs = rs[j];
-          fi = ri[j];
-        }
-      out_s[(long)q * K + kk] = fs;
-      out_i[(long)q * K + kk] = fi == 0x7fffffff ? -1 : fi;
-      rs[0] = fs;
-      ri[0] = fi;
+      out_s[(long)q * K + kk] = bs;
+      out_i[(long)q * K + kk] = bi == kNoCand ? -1 : bi;  // (-inf, id >= 0) is a hit, not a pad
     }
-    __syncthreads();
-    prev_s = rs[0];
-    prev_i = ri[0];
-    __syncthreads();
+    prev_s = bs;
+    prev_i = bi;
+    __syncthreads();  // rs / ri are rewritten by the next round
   }
-  (void)last;
 }
 
 }  // namespace

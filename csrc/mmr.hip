@@ -2,7 +2,7 @@
 //   mmr_i = lam * rel_i - (1 - lam) * m_i,   m_i = max over the already selected s of sim(i, s)
 // with sim(i, j) = dot(c_i, c_j) / (cnorm[id_i] * cnorm[id_j] + 1e-9), the form of knn.hip, and the
 // pick of a round the present, not yet selected candidate with the largest mmr, ties to the lower
-// position: better() of common.h on (mmr, position).  m_i is 0 in round 0 and is ASSIGNED from the
+// position: better() of topk.h on (mmr, position).  m_i is 0 in round 0 and is ASSIGNED from the
 // first pick (a negative similarity stays negative).  The kernel does not know the query: rel is an
 // input.  Candidate i is present iff 0 <= cand_id[i] < N and rel[i] is not NaN; an absent
 // candidate's row address is clamped to row 0 and what was computed from it is never used.  When the
@@ -29,13 +29,12 @@
 //
 // Nothing the device reads is trusted to index memory: ids outside [0, N) never form an address,
 // positions and K are bounded by the host's checks (1 <= K <= C <= 64).
-#include "common.h"
 #include "kernels.h"
+#include "topk.h"
 
 namespace {
 
 constexpr int MAXC = kLkMmrMaxCand;
-constexpr int NONE = 0x7fffffff;
 
 __global__ __launch_bounds__(256) void mmr_select_kernel(
     const bf16_t* __restrict__ corpus, const float* __restrict__ cnorm, long N, int D,
@@ -136,9 +135,9 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(
     const float v = lr - pen;
     const bool ok = avail && v == v;
     float bs = ok ? v : -INFINITY;
-    int bi = ok ? lane : NONE;
+    int bi = ok ? lane : kNoCand;
     wave_argmax(bs, bi);
-    if (bi == NONE) {  // nobody left (every lane sees the same bi): the rest are pads
+    if (bi == kNoCand) {  // nobody left (every lane sees the same bi): the rest are pads
       for (int k = rr + lane; k < K; k += 64) {
         o_pos[k] = -1;
         o_id[k] = -1;

@@ -255,16 +255,7 @@ def knn_merge(cand_s, cand_i, K: int):
     with id < 0 or a NaN score is absent, (-inf, -1) pads."""
     if use_hip(cand_s):
         return tuple(lib().knn_merge(cand_s.contiguous(), cand_i.contiguous(), K))
-    nq = cand_s.shape[0]
-    out_s = torch.full((nq, K), float("-inf"))
-    out_i = torch.full((nq, K), -1, dtype=torch.int32)
-    for r in range(nq):
-        pairs = [(s, i) for s, i in zip(cand_s[r].tolist(), cand_i[r].tolist()) if i >= 0 and s == s]
-        pairs.sort(key=lambda p: (-p[0], p[1]))
-        for j, (s, i) in enumerate(pairs[:K]):
-            out_s[r, j] = s
-            out_i[r, j] = i
-    return out_s, out_i
+    return ref.knn_merge(cand_s, cand_i, K)
 
 
 def bm25_topk(term_ptr, post_doc, post_tf, kn, q_ptr, q_term, q_w, K: int):

@@ -252,6 +252,21 @@ def stable_topk(scores, K):
     return out_s, out_i
 
 
+def knn_merge(cand_s, cand_i, K):
+    """The K best of each row's (score, id) candidates, (score desc, id asc); a candidate with
+    id < 0 or a NaN score is absent, (-inf, -1) pads follow."""
+    nq = cand_s.shape[0]
+    out_s = torch.full((nq, K), float("-inf"))
+    out_i = torch.full((nq, K), -1, dtype=torch.int32)
+    for r in range(nq):
+        pairs = [(s, i) for s, i in zip(cand_s[r].tolist(), cand_i[r].tolist()) if i >= 0 and s == s]
+        pairs.sort(key=lambda p: (-p[0], p[1]))
+        for j, (s, i) in enumerate(pairs[:K]):
+            out_s[r, j] = s
+            out_i[r, j] = i
+    return out_s, out_i
+
+
 def knn_topk(corpus, cnorm, queries, qnorm, K):
     sc = cosine_scores(corpus.float().cpu(), cnorm.cpu(), queries.float().cpu(), qnorm.cpu())
     return stable_topk(sc, K)

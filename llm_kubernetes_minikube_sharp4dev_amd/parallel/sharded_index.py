@@ -77,15 +77,7 @@ class ShardedKnnIndex:
         return self._search_group(queries, k)
 
     def _search_group(self, queries: torch.Tensor, k: int):
-        q = queries.to(self.corpus.device, self.corpus.dtype).contiguous()
-        qn = ops.row_norms(q)
-        if self.corpus.shape[0]:
-            s, i = ops.knn_topk(self.corpus, self.norms, q, qn, k)
-            s, i = s.to(q.device), i.to(q.device)
-            i = torch.where(i >= 0, i + self.offset, i)
-        else:
-            s = torch.full((q.shape[0], k), float("-inf"), device=q.device)
-            i = torch.full((q.shape[0], k), -1, dtype=torch.int32, device=q.device)
+        s, i = self.local(queries, k)
         if self.world == 1:
             return s, i
         ss = [torch.empty_like(s) for _ in range(self.world)]

@@ -15,7 +15,7 @@ cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-Icsrc", "--offload-arch=gfx
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, []
 for line in out.splitlines():
-    m = re.search(r"remark: (?:\s*)([^\[]+?) \[-Rpass", line)
+    m = re.search(r"remark: \s*(.+) \[-Rpass", line)  # keys such as "LDS Size [bytes/block]" hold a bracket
     if not m:
         continue
     txt = m.group(1).strip()
