@@ -2,14 +2,19 @@
 single MI355X (each maps the other's staging / signal buffers through HIP IPC, as the
 ranks of an 8-GPU node map their peers' over xGMI).  Exact sums of small integers
 (bf16-representable), several sizes, in place, and replayed from a captured hipGraph."""
+import functools
 import os
 import socket
+import sys
 import tempfile
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ar_probes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 # up to 8 ranks share the ONE device here: keep every rank's spinning workgroups co-resident
@@ -24,9 +29,16 @@ def _free_port():
     return p
 
 
-def _vals(n, r, it=0, mod=32):
-    # sums over up to 8 ranks stay below 256: exact in bf16
-    return ((torch.arange(n) * (r + 1) + it) % mod).to(torch.bfloat16)
+@functools.lru_cache(maxsize=4)
+def _layout(n, it):
+    return ar_probes.layout(8, n, seed=it)[0]
+
+
+def _vals(n, r, it=0):
+    # rank r's share of the layout probe (tests/ar_probes.py): 2^r * bit(r, i), the bits without a
+    # period in i, so a read from the wrong place changes the sum; sums over up to 8 ranks stay
+    # below 256: exact in bf16
+    return _layout(n, it)[r]
 
 
 def _worker(rank, world, port, out_dir):
