@@ -123,6 +123,18 @@ class Scheduler:
                 seq.last_hash = parent
                 seq.num_cached_prefix = max(seq.num_cached_prefix, seq.num_computed)
 
+    def _drop_prefix(self, seq: Sequence):
+        """Give back the prefix-cache hit of a waiting sequence whose admission then failed: a
+        sequence that waits holds no blocks.  (Held, they can be the very blocks a preempted
+        sequence put in front of it lacks: with nothing running, that one was then finished as
+        "kv cache too small" in a pool that fits it.)  The blocks stay cached for the next try."""
+        if not seq.block_table:
+            return
+        self.release(seq)
+        seq.num_computed = 0
+        seq.num_hashed_blocks = 0
+        seq.last_hash = 0
+
     # -------------------------------------------------------------- schedule
     @staticmethod
     def _generating(seq: Sequence) -> bool:
@@ -195,6 +207,8 @@ class Scheduler:
                     self.release(seq)
                     seq.status = Status.FINISHED
                     seq.finish_reason = "error: kv cache too small"
+                else:
+                    self._drop_prefix(seq)
                 break
             self.waiting.popleft()
             seq.status = Status.RUNNING
