@@ -178,6 +178,54 @@ def case_logprobs(R=128, n=20, V=128256):
             "sample_us": ts * 1e6}
 
 
+def case_prompt_logprobs(R, H, V, iters=7):
+    """Prompt log-probabilities of R hidden rows: the fused LM-head log-softmax kernel
+    (ops.lm_head_logprobs) against the unfused route -- ops.linear to bf16 logits [R, Vpad], then
+    ops.token_logprobs with n = 0 over every row.  Cold weights: a buffer larger than the Infinity
+    Cache is rewritten before every timed call (outside the events).  Peak memory: the allocator's
+    high-water mark of one call above what was allocated before it."""
+    from llm_kubernetes_minikube_sharp4dev_amd.models.configs import pad_vocab
+
+    g = torch.Generator(device=DEV).manual_seed(0)
+    w = torch.randn(pad_vocab(V), H, device=DEV, generator=g).mul_(H ** -0.5).to(torch.bfloat16)
+    x = torch.randn(R, H, device=DEV, generator=g).to(torch.bfloat16)
+    tgt = torch.randint(0, V, (R,), dtype=torch.int32, device=DEV, generator=g)
+    rows = torch.arange(R, dtype=torch.int32, device=DEV)
+    ws = ops.lm_head_logprobs_workspace(R, V, DEV)
+    flush = torch.empty(640 << 20, dtype=torch.uint8, device=DEV)
+
+    def fused():
+        return ops.lm_head_logprobs(x, w, tgt, V, ws)[0]
+
+    def unfused():
+        lg = ops.linear(x, w)
+        return ops.token_logprobs(lg[:, :V], tgt, rows, 0)[0]
+
+    def measure(fn):
+        fn()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ts = []
+        for _ in range(iters):
+            flush.add_(1)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b) * 1e-3)
+        return statistics.median(ts), (torch.cuda.max_memory_allocated() - base) / 2**20
+
+    diff = (fused() - unfused()).abs().max().item()  # bf16-rounded logits on the unfused side
+    tf, mf = measure(fused)
+    tu, mu = measure(unfused)
+    tf2, _ = measure(fused)  # the fused arm again: the spread of the same code in the same process
+    return {"case": f"prompt_logprobs R{R} H{H} V{V}", "us": tf * 1e6, "fused_again_us": tf2 * 1e6,
+            "TFLOP/s": 2 * R * V * H / tf / 1e12, "unfused_us": tu * 1e6, "fused_peak_MiB": mf, "unfused_peak_MiB": mu,
+            "ws_MiB": ws.numel() * 4 / 2**20, "max_abs_diff": diff}
+
+
 def case_gemm(M, N, K, layout="NT"):
     """hipBLASLt via torch: NT = x @ W^T with W [N,K] (nn.Linear layout), NN = x @ W with W [K,N]."""
     a = torch.randn(M, K, device=DEV, dtype=torch.bfloat16)
@@ -294,6 +342,8 @@ CASES = {
     "norm": lambda: [case_rmsnorm(), case_silu(), case_silu(3584), case_silu(4096), case_silu(128), case_silu(4096, 1792),
                      case_silu_down(3584), case_silu_down(4096)],
     "logprobs": lambda: [case_logprobs(R, n) for R in (1, 128) for n in (0, 20)],
+    "prompt_logprobs": lambda: [case_prompt_logprobs(4096, 4096, 128256), case_prompt_logprobs(256, 4096, 128256),
+                                case_prompt_logprobs(4096, 768, 50272)],
     "knn": lambda: [case_knn(), case_knn(nq=8), case_knn(N=1_000_000, nq=8), case_knn(N=1_000_000, nq=128)],
     "gemm": lambda: [case_gemm(64, 6144, 4096), case_gemm(64, 28672, 4096), case_gemm(64, 4096, 14336),
                      case_gemm(32768, 6144, 4096), case_gemm(32768, 28672, 4096), case_gemm(32768, 4096, 14336)],

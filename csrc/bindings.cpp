@@ -991,6 +991,32 @@ std::vector<at::Tensor> token_logprobs(const at::Tensor& logits, const at::Tenso
   return {chosen, top_lp, top_id};
 }
 
+// Fused LM head + log-softmax at the target ids (csrc/lm_head_lse.hip): see kernels.h.  ws: the caller's
+// f32 workspace (>= lm_head_logprobs_ws_floats(R, vocab) elements), or none: allocated for this call.
+std::vector<at::Tensor> lm_head_logprobs(const at::Tensor& x, const at::Tensor& w, const at::Tensor& targets,
+                                         int64_t vocab, const c10::optional<at::Tensor>& ws_) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_LASTDIM(x); CHECK_CUDA(w); CHECK_BF16(w); CHECK_CONTIG(w);
+  CHECK_CUDA(targets); CHECK_I32(targets); CHECK_CONTIG(targets);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "lm_head_logprobs: x [R, H], w [Vpad, H]");
+  TORCH_CHECK(targets.dim() == 1 && targets.numel() == x.size(0), "lm_head_logprobs: targets [R]");
+  TORCH_CHECK(vocab >= 1 && vocab <= w.size(0), "lm_head_logprobs: vocab ", vocab, " outside 1..", w.size(0));
+  TORCH_CHECK(x.size(0) <= (1 << 22) && w.size(0) < (1ll << 31), "lm_head_logprobs: too many rows");
+  const int R = x.size(0), V = (int)vocab, H = x.size(1);
+  CHECK_RC(std::min(lk_lm_head_logprobs_supported(R, V, (int)w.size(0), H), 0), "lm_head_logprobs");
+  at::Tensor lp = at::empty({R}, x.options().dtype(at::kFloat));
+  at::Tensor lse = at::empty({R}, x.options().dtype(at::kFloat));
+  if (R == 0) return {lp, lse};
+  check_rows16(x, "x"); check_rows16(w, "w");
+  const long need = lk_lm_head_logprobs_ws_floats(R, V);
+  at::Tensor ws = ws_ ? *ws_ : at::empty({need}, x.options().dtype(at::kFloat));
+  CHECK_CUDA(ws); CHECK_F32(ws); CHECK_CONTIG(ws);
+  TORCH_CHECK(ws.numel() >= need, "lm_head_logprobs: workspace of ", ws.numel(), " floats, needs ", need);
+  int rc = lk_lm_head_logprobs(bp(x), R <= 1 ? (long)H : x.stride(0), bp(w), R, V, H, ip(targets), ws.data_ptr<float>(),
+                               lp.data_ptr<float>(), lse.data_ptr<float>(), cur_stream());
+  CHECK_RC(rc, "lm_head_logprobs");
+  return {lp, lse};
+}
+
 // Token masks of schema-constrained rows (csrc/token_mask.hip lk_mask_logits): see kernels.h
 at::Tensor mask_logits(const at::Tensor& logits, const at::Tensor& pool, const at::Tensor& mask_row,
                        const c10::optional<at::Tensor>& out_) {
@@ -1273,6 +1299,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("select_tokens", &select_tokens, "", py::arg("logits"), py::arg("temps") = py::none(), py::arg("seed") = 0, py::arg("step") = 0, py::arg("out") = py::none());
   m.def("repeat_penalty_", &repeat_penalty_);
   m.def("token_logprobs", &token_logprobs, "", py::arg("logits"), py::arg("ids"), py::arg("rows"), py::arg("n"));
+  m.def("lm_head_logprobs", &lm_head_logprobs, "", py::arg("x"), py::arg("w"), py::arg("targets"), py::arg("vocab"),
+        py::arg("ws") = py::none());
+  m.def("lm_head_logprobs_ws_floats", [](int64_t R, int64_t V) { return (int64_t)lk_lm_head_logprobs_ws_floats((int)R, (int)V); });
+  m.def("lm_head_logprobs_plan", [](int64_t R, int64_t V) {
+    int bm, bn, s;
+    lk_lm_head_logprobs_plan((int)R, (int)V, &bm, &bn, &s);
+    return std::vector<int64_t>{bm, bn, s};
+  }, "(row tile, column tile, vocabulary slices) of an (R, V) call");
+  m.def("lm_head_logprobs_supported", [](int64_t R, int64_t V, int64_t Vpad, int64_t H) {
+    return lk_lm_head_logprobs_supported((int)R, (int)V, (int)Vpad, (int)H) > 0;
+  });
   m.def("mask_logits", &mask_logits, "", py::arg("logits"), py::arg("pool"), py::arg("mask_row"), py::arg("out") = py::none());
   m.def("sample", &sample, "", py::arg("logits"), py::arg("prm"), py::arg("hist"), py::arg("hist_len"),
         py::arg("seed") = 0, py::arg("out") = py::none(), py::arg("bias") = py::none());

@@ -57,12 +57,20 @@ def _provenance():
     return provenance
 
 
+# Extra code-generation flags of single kernel files.  lm_head_lse.hip: no packed-fp32 VALU ops
+# (v_pk_add / mul / fma_f32) in its softmax epilogue -- scalar fp32 only, the same bits on every run.
+FILE_FLAGS = {
+    "lm_head_lse.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def _codegen_flags(debug: bool = False) -> tuple[list[str], list[str]]:
     """Flags that shape the generated code (no include paths of the local install)."""
     common = ["-O3", "-fPIC", "-std=c++17"]
     if debug:
         common += ["-DLK_DEBUG", "-g"]
     kern = common + [f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-ffp-contract=fast"]
+    kern += [f"{name}:{' '.join(flags)}" for name, flags in sorted(FILE_FLAGS.items())]
     bind = common + [f"--offload-arch={ARCH}", "-DTORCH_API_INCLUDE_EXTENSION_H", f"-DTORCH_EXTENSION_NAME={EXT_NAME}",
                      "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
     return kern, bind
@@ -117,7 +125,7 @@ def build(clean: bool = False, jobs: int | None = None, verbose: bool = False, d
     jobs_list = []
     for src in sorted(CSRC.glob("*.hip")):
         obj = BUILD / (src.stem + ".o")
-        jobs_list.append((src, obj, [hipcc, *kern_flags, "-c", str(src), "-o", str(obj)]))
+        jobs_list.append((src, obj, [hipcc, *kern_flags, *FILE_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)]))
     bsrc = CSRC / "bindings.cpp"
     bobj = BUILD / "bindings.o"
     jobs_list.append((bsrc, bobj, [hipcc, *bind_flags, "-x", "hip", "-c", str(bsrc), "-o", str(bobj)]))

@@ -244,6 +244,23 @@ int lk_sample(float* logits, long ls, int B, int V, const int* prm, int pw, cons
 int lk_token_logprobs(const void* logits, int is_bf16, long ls, int B, int V, const int* rows, int R,
                       const int* ids, int n, float* chosen_lp, float* top_lp, int* top_id, hipStream_t st);
 
+// lm_head_lse.hip
+// Fused LM head + log-softmax (docs/prompt_logprobs.md): logit[r, v] = sum_k x[r, k] * w[v, k] in fp32
+// (never rounded, never stored), lse[r] = logsumexp over v < V, lp[r] = logit[r, targets[r]] - lse[r]
+// (-inf for a target outside [0, V)).  x: [R, H] bf16, row stride ldx (ldx % 8 == 0, 16-byte aligned);
+// w: [>= V, H] bf16 dense, rows >= V (vocabulary padding) are never read.  Needs H % 64 == 0 and
+// H >= 64 (one K tile of the main loop), H <= 65536, 1 <= V <= 2^30, R <= 2^22; any V (ragged last
+// column tile) and any R.  ws: lk_lm_head_logprobs_ws_floats(R, V) floats owned by the caller, one
+// (max, sumexp, target) triple per row and vocabulary slice; written and read by this call only.
+// Two launches (slices, then the merge in slice order); R == 0 launches nothing.
+// plan: row tile, column tile and the number of vocabulary slices of an (R, V) call; slice s of S
+// covers the column tiles [s * nct / S, (s + 1) * nct / S), nct = ceil(V / column tile).
+void lk_lm_head_logprobs_plan(int R, int V, int* row_tile, int* col_tile, int* slices);
+int lk_lm_head_logprobs_supported(int R, int V, int Vpad, int H);  // 1, or < 0: R (-1), V (-2), H (-3)
+long lk_lm_head_logprobs_ws_floats(int R, int V);
+int lk_lm_head_logprobs(const bf16_t* x, long ldx, const bf16_t* w, int R, int V, int H, const int* targets,
+                        float* ws, float* lp, float* lse, hipStream_t st);
+
 // token_mask.hip
 // Token masks of schema-constrained rows: dst[b][v] = f32(src[b][v]) (bit-exact) where
 // mask_row[b] < 0 or bit v & 31 of pool[mask_row[b] * words + (v >> 5)] is set, else -inf, for

@@ -50,7 +50,7 @@ def _jump_ok(p: SamplingParams) -> bool:
     presence or frequency penalty reads the device history ring the sampler kernel appends to
     (host-appended tokens would be missing from it), and no log-probabilities are asked for (a
     host-appended token has no logits row of its own to take them from)."""
-    return p.logits_processor is not None and not p.reads_ring and not p.logprobs
+    return p.logits_processor is not None and not p.reads_ring and not p.logprobs and not p.prompt_logprobs
 
 
 def _small_buckets() -> tuple:
@@ -113,6 +113,12 @@ class LLMEngine:
                     req_id: Optional[str] = None, on_token: Optional[Callable] = None) -> Sequence:
         params = params or SamplingParams()
         seq = Sequence(list(prompt_ids), params)
+        if params.prompt_logprobs:
+            tp = getattr(self.model, "tp", None)
+            if tp is not None and tp.enabled:
+                # the vocabulary-sharded LM head would need an (lse, target) merge across ranks
+                raise ValueError("prompt_logprobs is not supported with tensor parallelism")
+            seq.prompt_logprobs = [None] * len(seq.prompt_ids)
         if req_id:
             seq.req_id = req_id
         seq.on_token = on_token
@@ -224,6 +230,9 @@ class LLMEngine:
                 ev0 = torch.cuda.Event(enable_timing=True)  # GPU-side step start (after earlier work)
                 ev0.record()
             rows, out = self.runner.forward_logits(batch.items, greedy)
+            # prompt log-probabilities of this step's prefill chunks (device), if any request asks
+            plp = (self.runner.take_prompt_logprobs()
+                   if any(sq.params.prompt_logprobs for sq, _, _ in batch.items) else None)
             note, self.trace_note = self.trace_note, ""
             for seq, start, n in batch.items:
                 seq.num_computed = start + n
@@ -231,12 +240,18 @@ class LLMEngine:
                 if seq.step_first is None:
                     seq.step_first = self.launches
             self.launches += 1
-            return [batch, rows, out, greedy, ts, t0, time.perf_counter(), (ev0, note, starved)]
+            return [batch, rows, out, greedy, ts, t0, time.perf_counter(), (ev0, note, starved), plp]
 
     def _sample(self, launched):
-        batch, rows, out, greedy, ts, t0, t1, ev0n = launched
+        batch, rows, out, greedy, ts, t0, t1, ev0n, plp = launched
         ev0 = ev0n[0]
         host = ev = ids = lps = None
+        staged = plp is not None and plp[1].is_cuda
+        if staged:
+            # to pinned memory under the step's ids event (recorded below): no earlier device wait
+            h = torch.empty(plp[1].shape, dtype=plp[1].dtype, pin_memory=True)
+            h.copy_(plp[1], non_blocking=True)
+            plp = (plp[0], h)
         if rows:
             seqs = [s for s, _ in rows]
             ids = out if greedy else self.sampler(out, [s.params for s in seqs], [s.output_ids for s in seqs],
@@ -264,20 +279,24 @@ class LLMEngine:
                     s.num_inflight, s.inflight_row = 1, i
             self.runner.prev_ids = ids
             self.runner.prev_sampled_rows = 0 if greedy else len(rows)
-        elif ev0 is not None:
+        elif ev0 is not None or staged:
             # a step with no sampled rows (a prompt chunk that does not end its prompt): its end
             # still bounds the traced GPU time, so the next step's idle is not charged with it
-            ev = torch.cuda.Event(enable_timing=True)
+            ev = torch.cuda.Event(enable_timing=ev0 is not None)
             ev.record()
-        return (batch, rows, host, ev, ts, t0, t1, time.perf_counter(), ev0n, lps)
+        return (batch, rows, host, ev, ts, t0, t1, time.perf_counter(), ev0n, lps, plp)
 
     def _collect(self, pending) -> list:
-        batch, rows, host, ev, ts, t0, t1, t1s, (ev0, launched_note, starved), lps = pending
+        batch, rows, host, ev, ts, t0, t1, t1s, (ev0, launched_note, starved), lps, plp = pending
         t2 = time.perf_counter()
-        if rows and ev is not None:
+        if (rows or plp is not None) and ev is not None:
             ev.synchronize()  # outside the lock: aborts and admissions never wait on the device
         with self.lock:
             out = []
+            if plp is not None:
+                # at their prompt positions: a recompute after a preemption writes the same values again
+                for (seq, pos), v in zip(plp[0], plp[1].tolist()):
+                    seq.prompt_logprobs[pos] = v
             if rows:
                 ids = host.tolist()
                 now = t2 = time.perf_counter()

@@ -127,6 +127,9 @@ class ModelRunner:
         self.graphs: dict = {}
         self._graph_pool = None
         self._ws = None
+        self._lp_ws = None     # workspace of the fused LM-head log-softmax kernel (prompt logprobs)
+        self._score = []       # [(seq, prompt position)] of the prepared step's prompt-logprob rows
+        self.prompt_lp = None  # their log-probabilities (device f32), until take_prompt_logprobs()
         self.step_hook = None
         self.prev_ids: Optional[torch.Tensor] = None  # previous step's sampled ids (device)
         self.prev_sampled_rows = 0  # rows of prev_ids sampled on the driver only (non-greedy step)
@@ -230,6 +233,23 @@ class ModelRunner:
         pm = self._ws[1][: n * 2].view(B, self.hq, ms, 2)
         return po, pm
 
+    def _score_ws(self, R: int):
+        """This runner's workspace of the fused LM-head kernel for R rows (grown on demand)."""
+        if self.device.type != "cuda":
+            return None
+        V = self.model.vocab_local
+        need = ops.lib().lm_head_logprobs_ws_floats(R, V)
+        if self._lp_ws is None or self._lp_ws.numel() < need:
+            self._lp_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._lp_ws
+
+    def take_prompt_logprobs(self):
+        """([(seq, prompt position)], lp f32 [n] on the device) of the step just run, or None."""
+        if self.prompt_lp is None:
+            return None
+        out, self.prompt_lp = (self._score, self.prompt_lp), None
+        return out
+
     def _slots(self, table, start, n):
         pos = np.arange(start, start + n, dtype=np.int64)
         blk = np.asarray(table, dtype=np.int64)[pos // self.bs]
@@ -324,6 +344,7 @@ class ModelRunner:
         return 1 < n <= EXTEND_AS_DECODE and start >= len(seq.prompt_ids) and seq.num_inflight == 0
 
     def _prepare(self, items):
+        self._score = []
         if (self.use_graphs and items and all(self._as_decode(*it) for it in items)
                 and sum(n for _, _, n in items) <= self.graph_sizes[-1]):
             return self._prepare_graph(items)
@@ -332,9 +353,17 @@ class ModelRunner:
         ids, pos, slots = [], [], []
         q_lens, ctx, tables = [], [], []
         rows = []
+        score_rows, score_tgt, score = [], [], []
         r = 0
         for seq, start, n in pre:
             ids.extend(seq.tokens(start, start + n))
+            if seq.params.prompt_logprobs:
+                # rows whose next token is a known prompt token: row of position p scores prompt[p + 1]
+                P = len(seq.prompt_ids)
+                for p in range(start, min(start + n, P - 1)):
+                    score_rows.append(r + p - start)
+                    score_tgt.append(seq.prompt_ids[p + 1])
+                    score.append((seq, p + 1))
             s, p = self._slots(seq.block_table, start, n)
             slots.append(s)
             pos.append(p)
@@ -363,6 +392,10 @@ class ModelRunner:
                         ctx_d=ctx_d, tables_d=tables_d,
                         num_decode=nd, logits_rows=np.asarray([row for _, row in rows], dtype=np.int64),
                         gather=self._gather(dec, r - nd) if dec else None, shared_len=shared)
+        if score:
+            si.score_rows = np.asarray(score_rows, dtype=np.int64)
+            si.score_targets = np.asarray(score_tgt, dtype=np.int32)
+        self._score = score
         return si, rows
 
     def _prepare_graph(self, items):
@@ -402,7 +435,10 @@ class ModelRunner:
             host.update(bt_d=si.tables_d, ctx_d=si.ctx_d)
             if si.shared_len:
                 host["shared"] = np.asarray([si.shared_len], dtype=np.int32)
-        if len(si.logits_rows):
+        if len(si.score_rows):  # prompt-logprob rows ride behind the sampled rows in one index list
+            host["logits"] = np.concatenate([np.asarray(si.logits_rows, dtype=np.int64), si.score_rows])
+            host["score_tgt"] = si.score_targets
+        elif len(si.logits_rows):
             host["logits"] = si.logits_rows
         if si.gather is not None:
             host.update(g_dst=si.gather[0], g_src=si.gather[1])
@@ -419,6 +455,7 @@ class ModelRunner:
             if si.shared_len:
                 self._cascade_meta(meta, si.num_decode, d["shared"])
         meta.logits_idx = d.get("logits")
+        meta.score_targets = d.get("score_tgt")
         ids = d["ids"]
         if si.gather is not None:
             self._apply_gather(ids, d["g_dst"], d["g_src"])
@@ -449,6 +486,7 @@ class ModelRunner:
         """Run one step on this rank; returns logits [R, V] f32, or int32 token ids [R]
         for a greedy step (None if no rows)."""
         self._sync_prev(si)
+        self.prompt_lp = None
         if si.decode_graph:
             out = self._graph_execute(si)
         else:
@@ -457,6 +495,14 @@ class ModelRunner:
                 self.model(ids, meta, self.kv_caches)  # partial prefill chunks only: KV write, no logits
                 return None
             h = self.model(ids, meta, self.kv_caches)
+            if meta.score_targets is not None:
+                # the first len(logits_rows) hidden rows are sampled as ever; the rest go through the
+                # fused LM-head log-softmax kernel (no [rows, vocab] logits)
+                ns = len(si.logits_rows)
+                self.prompt_lp = self.model.token_logprobs(h[ns:], meta.score_targets, self._score_ws(h.shape[0] - ns))
+                if ns == 0:
+                    return None
+                h = h[:ns]
             out = self.model.greedy(h) if si.greedy else self.model.logits(h, dtype=self.logits_dtype)
         if si.greedy:
             self.prev_ids = out  # every TP rank holds the same greedy ids (distributed argmax)
@@ -601,3 +647,6 @@ class StepInputs:
     gather: Optional[tuple] = None        # (dst rows, src rows): in-flight ids from the previous step
     shared_len: int = 0                   # cascade: leading keys shared by every decode row
     prev_bcast: int = 0                   # TP: rows of driver-sampled previous ids to broadcast
+    # prompt log-probabilities: step rows whose next token is a known prompt token, and those tokens
+    score_rows: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=np.int64))
+    score_targets: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=np.int32))

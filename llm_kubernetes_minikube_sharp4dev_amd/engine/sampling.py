@@ -49,6 +49,8 @@ class SamplingParams:
     # token's, and the top_logprobs (0..20) most likely tokens' per generated token
     logprobs: bool = False
     top_logprobs: int = 0
+    # log-probability of every prompt token given the tokens before it (docs/prompt_logprobs.md)
+    prompt_logprobs: bool = False
     # sampler controls (docs/sampling.md): min_p keeps a candidate while p_i >= min_p * p_max;
     # presence / frequency are subtracted per unique token / per occurrence in the repeat window;
     # logit_bias {token id: f32} is added to the logits before anything else

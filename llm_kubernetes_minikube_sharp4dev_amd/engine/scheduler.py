@@ -113,7 +113,9 @@ class Scheduler:
         self.waiting.appendleft(seq)
 
     def _admit_prefix(self, seq: Sequence):
-        if seq.num_computed == 0 and not seq.block_table:
+        # (a request for prompt log-probabilities computes every prompt row: no cache hit; it still
+        # publishes its blocks)
+        if seq.num_computed == 0 and not seq.block_table and not seq.params.prompt_logprobs:
             ids = seq.tokens(0, seq.length)
             blocks, parent = self.alloc.match_prefix(ids)
             if blocks:

@@ -27,6 +27,9 @@ class Sequence:
     # one (chosen logprob, [(token id, logprob), ...]) per output token when params.logprobs is
     # set (len(logprobs) == len(output_ids) at all times), else empty
     logprobs: list = field(default_factory=list)
+    # params.prompt_logprobs: one entry per prompt token, [None, log p(prompt[1] | prompt[:1]), ...],
+    # filled chunk by chunk as the prompt is prefilled (None until computed); else empty
+    prompt_logprobs: list = field(default_factory=list)
     block_table: list = field(default_factory=list)
     num_computed: int = 0          # tokens whose K/V are in the cache
     num_cached_prefix: int = 0     # tokens served by the prefix cache at admission

@@ -69,6 +69,8 @@ class AttnMeta:
     pp_ml: Optional[torch.Tensor] = None
     # rows whose hidden state feeds the LM head (last token of each prefill + decode rows)
     logits_idx: Optional[torch.Tensor] = None
+    # prompt log-probabilities: the target token ids (int32) of the trailing rows of logits_idx
+    score_targets: Optional[torch.Tensor] = None
     # context parallelism (paged_attention's cp_group): the block tables / ctx_lens above
     # describe THIS rank's contiguous shard of every sequence's keys, whose first key sits
     # at global position cp_key_start_{p,d}[b] (host ints); queries are replicated

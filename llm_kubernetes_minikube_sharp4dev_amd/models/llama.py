@@ -428,6 +428,13 @@ class LlamaModel(nn.Module):
         """Greedy next tokens [R] int32 without materialising gathered fp32 logits."""
         return self.tp.greedy_ids(self.head(hidden), self.vocab_lo)
 
+    def token_logprobs(self, hidden_rows: torch.Tensor, targets: torch.Tensor, ws=None) -> torch.Tensor:
+        """log p(targets[r] | row r) f32 [R] from final-normed hidden rows, by the fused LM-head
+        kernel: no [R, vocab] logits (docs/prompt_logprobs.md).  Not vocabulary-parallel."""
+        if self.tp.enabled:
+            raise RuntimeError("token_logprobs: the vocabulary-sharded LM head is not supported")
+        return ops.lm_head_logprobs(hidden_rows, self.lm_head, targets, self.vocab_local, ws)[0]
+
     # ------------------------------------------------------------------ HF checkpoint
     @torch.no_grad()
     def load_hf_state_dict(self, sd: dict):

@@ -117,6 +117,10 @@ class OPTModel(nn.Module):
     def greedy(self, hidden):
         return self.tp.greedy_ids(self.head(hidden), self.vocab_lo)
 
+    def token_logprobs(self, hidden_rows, targets, ws=None):
+        """log p(targets[r] | row r) f32 [R] by the fused LM-head kernel (docs/prompt_logprobs.md)."""
+        return ops.lm_head_logprobs(hidden_rows, self.lm_head, targets, self.vocab_local, ws)[0]
+
     @torch.no_grad()
     def load_hf_state_dict(self, sd: dict):
         """HuggingFace ``OPTForCausalLM`` names (``model.decoder.*``)."""

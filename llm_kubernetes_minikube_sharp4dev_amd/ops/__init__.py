@@ -360,6 +360,28 @@ def token_logprobs(logits, ids, rows, n: int):
     return ref.token_logprobs(logits, ids, rows, n)
 
 
+def lm_head_logprobs_plan(R: int, vocab: int):
+    """(row tile, column tile, vocabulary slices) of the fused LM-head kernel for ``R`` rows; slice
+    ``s`` of ``S`` covers the column tiles ``[s * nct // S, (s + 1) * nct // S)``."""
+    return tuple(lib().lm_head_logprobs_plan(int(R), int(vocab)))
+
+
+def lm_head_logprobs_workspace(R: int, vocab: int, device) -> torch.Tensor:
+    """The f32 workspace of an ``lm_head_logprobs`` call of up to ``R`` rows: O(R * slices)."""
+    return torch.empty(lib().lm_head_logprobs_ws_floats(int(R), int(vocab)), dtype=torch.float32, device=device)
+
+
+def lm_head_logprobs(hidden, weight, targets, vocab: int, ws=None):
+    """Log-probability of ``targets`` [R] (int32) under the LM head, without materialising a logit:
+    ``logit = hidden [R, H] @ weight[:vocab].T`` in fp32 -> (lp f32 [R] = logit[r, targets[r]] -
+    lse[r], lse f32 [R] = logsumexp over the ``vocab`` real rows of ``weight``; its padding rows are
+    never read).  A target outside ``[0, vocab)`` gives ``-inf``.  ``ws``: a caller-owned workspace
+    (``lm_head_logprobs_workspace``), else one is allocated for the call.  docs/prompt_logprobs.md."""
+    if use_hip(hidden):
+        return tuple(lib().lm_head_logprobs(hidden, weight, targets, int(vocab), ws))
+    return ref.lm_head_logprobs(hidden, weight, targets, int(vocab))
+
+
 def mask_logits(logits, pool, mask_row, out=None):
     """Token masks of schema-constrained rows (docs/structured_outputs.md): an f32 copy of
     ``logits`` [B, V] (bf16 or f32, never modified unless ``out`` is ``logits``) in which every id

@@ -493,6 +493,20 @@ def token_logprobs(logits, ids, rows, n: int):
     return chosen, lp.gather(1, order), order.int()
 
 
+def lm_head_logprobs(hidden, weight, targets, vocab: int):
+    """fp32 reference of lk_lm_head_logprobs (csrc/lm_head_lse.hip): fp32 matmul against the first
+    ``vocab`` rows of ``weight``, ``log_softmax``, gather at ``targets`` -> (lp f32 [R], lse f32 [R]);
+    a target outside ``[0, vocab)`` gives ``-inf``."""
+    if not 1 <= int(vocab) <= weight.shape[0]:
+        raise ValueError(f"lm_head_logprobs: vocab {vocab} outside 1..{weight.shape[0]}")
+    logits = hidden.float() @ weight[:vocab].float().T
+    lse = torch.logsumexp(logits, dim=-1)
+    t = targets.long()
+    ok = (t >= 0) & (t < vocab)
+    lp = torch.log_softmax(logits, dim=-1).gather(1, t.clamp(0, vocab - 1)[:, None]).squeeze(1)
+    return torch.where(ok, lp, torch.full_like(lp, float("-inf"))), lse
+
+
 def mask_logits(logits, pool, mask_row, out=None):
     """fp32 reference of lk_mask_logits (csrc/token_mask.hip): ``out[b, v] = f32(logits[b, v])``
     (bit-exact) where ``mask_row[b] < 0`` or bit ``v & 31`` of ``pool[mask_row[b], v >> 5]`` is

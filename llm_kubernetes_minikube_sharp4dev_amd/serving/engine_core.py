@@ -13,7 +13,9 @@ with a compact binary protocol:
                   | ["rerank", rid, model, query, docs, activation]
   core -> client  ["tok", [[rid, [ids..], finished, reason, cached_prefix, error], ...], stats]
                     (an item of a request that asked for logprobs has a 7th element: one
-                    [chosen logprob, [[id, logprob], ...]] entry per id of the item)
+                    [chosen logprob, [[id, logprob], ...]] entry per id of the item; the accounting
+                    of a finished request that asked for prompt logprobs carries the list as
+                    "prompt_logprobs": [None, lp, ...])
                   | ["emb", rid, f32 bytes, rows, dim] | ["load", rid, meta] | ["err", rid, msg]
                   | ["rr", rid, f32 score bytes, n, pair tokens encoded]
 
@@ -74,6 +76,8 @@ def sp_to_wire(sp: SamplingParams) -> dict:
     d = {k: getattr(sp, k) for k in SP_FIELDS}
     if sp.logprobs:  # only when asked: every other request's frame is what it always was
         d["logprobs"], d["top_logprobs"] = True, int(sp.top_logprobs)
+    if sp.prompt_logprobs:  # likewise (docs/prompt_logprobs.md)
+        d["prompt_logprobs"] = True
     # the sampler controls likewise travel only when set (docs/sampling.md)
     for k in ("min_p", "presence_penalty", "frequency_penalty"):
         if getattr(sp, k) != 0.0:
@@ -86,8 +90,11 @@ def sp_to_wire(sp: SamplingParams) -> dict:
 def _accounting(seq) -> dict:
     """Per-request engine accounting sent with a request's last token (front-ends report it)."""
     q = (seq.step_first - seq.step_arrival) if getattr(seq, "step_first", None) is not None else None
-    return {"cached": seq.num_cached_prefix, "preempt": getattr(seq, "num_preemptions", 0),
-            "queued": q, "run": getattr(seq, "steps_run", None), "jumped": getattr(seq, "jumped", 0)}
+    acc = {"cached": seq.num_cached_prefix, "preempt": getattr(seq, "num_preemptions", 0),
+           "queued": q, "run": getattr(seq, "steps_run", None), "jumped": getattr(seq, "jumped", 0)}
+    if seq.params.prompt_logprobs:  # the requesting request's final frame carries the list
+        acc["prompt_logprobs"] = list(seq.prompt_logprobs)
+    return acc
 
 
 def _count_request(seq):
@@ -260,7 +267,12 @@ class EngineCore:
                 sp.logits_processor = json_logits_processor(h.tokenizer, fmt if isinstance(fmt, dict) else None)
             erid = f"c{conn.cid}-{rid}"
             conn.reqs[rid] = (h, erid)
-            h.engine.add_request(list(ids), sp, erid, lambda seq, tid, fin, rid=rid: conn.on_token(rid, seq, tid, fin))
+            try:
+                h.engine.add_request(list(ids), sp, erid, lambda seq, tid, fin, rid=rid: conn.on_token(rid, seq, tid, fin))
+            except ValueError as e:  # a request this engine refuses (e.g. prompt_logprobs under TP)
+                conn.reqs.pop(rid, None)
+                conn.post(["err", rid, str(e)])
+                return
             h.async_engine._wake.set()
         elif op == "abort":
             ent = conn.reqs.pop(msg[1], None)

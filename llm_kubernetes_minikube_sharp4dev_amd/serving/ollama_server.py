@@ -703,6 +703,22 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
             set_openai_controls(sp, b, h)
         except ValueError as e:
             return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
+        # echo (docs/prompt_logprobs.md): the prompt is returned in front of the completion, and with
+        # `logprobs` every prompt token's log-probability too; max_tokens 0 then means "score only"
+        echo = bool(b.get("echo"))
+        score_only = echo and b.get("max_tokens") == 0 and not isinstance(b.get("max_tokens"), bool)
+        if echo:
+            if b.get("stream"):
+                return JSONResponse({"error": {"message": "echo is not supported with stream",
+                                               "type": "invalid_request_error"}}, status_code=400)
+            if b.get("logprobs") is not None and b.get("logprobs") is not False:
+                if _tp_of(h) > 1:
+                    return JSONResponse({"error": {"message": "echo with logprobs is not supported with tensor "
+                                                              "parallelism (the LM head is vocabulary-sharded)",
+                                                   "type": "invalid_request_error"}}, status_code=400)
+                sp.prompt_logprobs = True
+            if score_only:
+                sp.max_tokens = 1  # one engine token, dropped below
         n_lp = b.get("logprobs")  # the legacy integer: the number of alternatives per token
         try:
             if isinstance(n_lp, bool):
@@ -712,19 +728,44 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
         except ValueError as e:
             return JSONResponse({"error": {"message": str(e).replace("top_logprobs", "logprobs"),
                                            "type": "invalid_request_error"}}, status_code=400)
-        seq = await h.async_engine.generate(ids, sp)
-        choice = {"index": 0, "text": h.tokenizer.decode(seq.output_ids), "finish_reason": seq.finish_reason}
+        try:
+            seq = await h.async_engine.generate(ids, sp)
+        except ValueError as e:  # the engine refused the request at admission
+            return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
+        if echo and getattr(seq, "error", None):
+            return JSONResponse({"error": {"message": seq.error, "type": "invalid_request_error"}}, status_code=400)
+        out_ids = [] if score_only else seq.output_ids
+        choice = {"index": 0, "text": h.tokenizer.decode(out_ids), "finish_reason": seq.finish_reason}
+        if echo:
+            choice["text"] = (b.get("prompt") or "") + choice["text"]
+            if score_only:
+                choice["finish_reason"] = "length"
         if sp.logprobs:
-            ent = lp_entries(h, seq)
+            ent = [] if score_only else lp_entries(h, seq)
             offs, raw = [], b""
+            if sp.prompt_logprobs:
+                # prompt tokens first: token_logprobs[0] and every prompt position's top_logprobs are null
+                entry = lp_entry_maker(h)
+                plp = list(seq.prompt_logprobs)
+                pre = [dict(entry(t, (plp[i] if i < len(plp) else None, [])), top_logprobs=None) for i, t in enumerate(ids)]
+                if pre:
+                    pre[0]["logprob"] = None
+                    if len(ids) > len(h.tokenizer.encode(b.get("prompt") or "", add_bos=False)):
+                        pre[0]["bytes"] = []  # the BOS the server added takes no room in `text`
+                ent = pre + ent
             for e in ent:
                 offs.append(len(raw.decode("utf-8", errors="replace")))
                 raw += bytes(e["bytes"])
             choice["logprobs"] = {"tokens": [e["token"] for e in ent], "token_logprobs": [e["logprob"] for e in ent],
-                                  "top_logprobs": [{t["token"]: t["logprob"] for t in e["top_logprobs"]} for e in ent],
+                                  "top_logprobs": [None if e["top_logprobs"] is None else
+                                                   {t["token"]: t["logprob"] for t in e["top_logprobs"]} for e in ent],
                                   "text_offset": offs}
-        return {"id": "cmpl-" + uuid.uuid4().hex[:12], "object": "text_completion", "created": int(time.time()),
+        resp = {"id": "cmpl-" + uuid.uuid4().hex[:12], "object": "text_completion", "created": int(time.time()),
                 "model": model, "choices": [choice]}
+        if echo:
+            resp["usage"] = {"prompt_tokens": len(ids), "completion_tokens": len(out_ids),
+                             "total_tokens": len(ids) + len(out_ids)}
+        return resp
 
     @app.post("/v1/embeddings")
     async def oa_emb(request: Request):

@@ -41,6 +41,7 @@ class _SeqView:
     output_ids: list = field(default_factory=list)
     # (chosen logprob, [(id, logprob), ...]) per output id of a request that asked (else empty)
     logprobs: list = field(default_factory=list)
+    prompt_logprobs: list = field(default_factory=list)  # of a request that asked: [None, lp, ...]
     num_cached_prefix: int = 0
     finish_reason: Optional[str] = None
     error: Optional[str] = None
@@ -58,6 +59,7 @@ class _SeqView:
             self.num_preemptions = acc.get("preempt") or 0
             self.steps_queued, self.steps_run = acc.get("queued"), acc.get("run")
             self.jumped = acc.get("jumped") or 0
+            self.prompt_logprobs = list(acc.get("prompt_logprobs") or [])
         else:  # (older cores: the cached-prefix count alone)
             self.num_cached_prefix = acc or 0
 
