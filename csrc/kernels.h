@@ -47,6 +47,15 @@ int lk_gemv_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, flo
                    int K, bf16_t* out, long ldo, bf16_t* res, long ldr, const int* positions, const float* cos_sin,
                    int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc, const int* slots, int BS, int neox, hipStream_t st);
 
+// gemv_decode_w8.hip (the same decode GEMV over FP8 weights: wq [N, K] OCP e4m3, one byte per weight,
+// wscale f32 [N] applied once to each finished fp32 dot product; K % 1024 == 0)
+int lk_gemv_w8_supported(int M, int N, int K, int mode);
+void lk_gemv_w8_set_plan(int pairs, int ksplit);  // measurement arms: pairs per wave (0: default), K split (-1: default)
+int lk_gemv_w8_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, float eps, const unsigned char* wq,
+                      const float* wscale, int M, int N, int K, bf16_t* out, long ldo, bf16_t* res, long ldr,
+                      const int* positions, const float* cos_sin, int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc,
+                      const int* slots, int BS, int neox, hipStream_t st);
+
 // GEMM part only (S >= 2): f32 partial slabs part[S][M][N], for a consumer that fuses the
 // split-K reduction (lk_splitk_rmsnorm, lk_splitk_rope_kv)
 int lk_wsgemm_set_variant(int M, int N, int K, int swiglu, int variant);  // -1 = back to the default

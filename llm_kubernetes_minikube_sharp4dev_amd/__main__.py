@@ -47,6 +47,9 @@ def _cfg(args):
         cfg.agent.fake_cluster = False
     if getattr(args, "index_cache", None):
         cfg.rag.cache_dir = args.index_cache
+    if getattr(args, "decode_weights", None):
+        # (through the environment too: the engine-core processes of the split server read it there)
+        os.environ["LK_ENGINE__DECODE_WEIGHTS"] = cfg.engine.decode_weights = args.decode_weights
     return cfg
 
 
@@ -563,6 +566,12 @@ def _tp_args(p):
                    help="with --tp: every rank on GPU 0 (gloo + IPC collectives; rehearses TP on a one-GPU box)")
 
 
+def _decode_weights_arg(p):
+    p.add_argument("--decode-weights", choices=("bf16", "fp8"), default=None,
+                   help="(default: engine.decode_weights of the config, bf16) fp8: decode steps of 1-2 rows stream "
+                        "e4m3 copies of the generator's weights (docs/decode_fp8.md); not with --tp")
+
+
 def main(argv=None):
     # a long-running server that dies in native code (a HIP runtime abort, a segfault in an
     # extension thread) leaves every thread's Python stack in its log
@@ -593,6 +602,7 @@ def main(argv=None):
                    help="split server: HTTP front-end processes (SO_REUSEPORT) in front of the engine core(s); "
                         "default 2 on GPUs, 0 (one process) on the CPU; 0 with --gpus > 1 = single-proxy router")
     _tp_args(p)
+    _decode_weights_arg(p)
     p.set_defaults(fn=cmd_serve)
     p = common(sub.add_parser("serve-core"), 0)
     p.add_argument("--socket", required=True)
@@ -640,6 +650,7 @@ def main(argv=None):
     p.add_argument("--kubeconfig", default=None)
     p.add_argument("--index-cache", default=None)
     _tp_args(p)
+    _decode_weights_arg(p)
     p.set_defaults(fn=cmd_all)
     p = sub.add_parser("index")
     p.add_argument("--config", default=None)

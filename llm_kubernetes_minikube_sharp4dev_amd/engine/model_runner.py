@@ -13,6 +13,7 @@ hipGraph-captured decode.
 from __future__ import annotations
 
 import bisect
+import gc
 import os
 from dataclasses import dataclass, field
 from typing import Optional
@@ -581,11 +582,22 @@ class ModelRunner:
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
-        # thread-local capture: a serving process's other threads (HTTP handlers, the
-        # embedding engine's own stream) may touch the device while a bucket is captured
-        with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
-            h = self.model(st["ids"], st["meta"], self.kv_caches)
-            st["logits"] = self.model.greedy(h) if greedy else self.model.logits(h, dtype=self.logits_dtype)
+        # No cyclic garbage collection inside the capture: a dead engine's graphs and events, freed by
+        # a collection that happens to fall between two captured launches, make HIP calls that a
+        # capturing thread may not make, and the process aborts in their destructors.  Collect
+        # before (torch.cuda.graph no longer does), hold the collector off until the capture ends.
+        gc_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            # thread-local capture: a serving process's other threads (HTTP handlers, the
+            # embedding engine's own stream) may touch the device while a bucket is captured
+            with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
+                h = self.model(st["ids"], st["meta"], self.kv_caches)
+                st["logits"] = self.model.greedy(h) if greedy else self.model.logits(h, dtype=self.logits_dtype)
+        finally:
+            if gc_on:
+                gc.enable()
         st["graph"] = g
         self.graphs[(B, greedy)] = st
         return st

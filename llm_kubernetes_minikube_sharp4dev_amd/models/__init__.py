@@ -1,6 +1,7 @@
 """Model construction: presets (``configs``), random-init or checkpoint weights."""
 from __future__ import annotations
 
+import os
 from pathlib import Path
 from typing import Optional
 
@@ -15,6 +16,9 @@ from .llama import LlamaModel
 from .opt import OPTModel
 
 
+DECODE_WEIGHTS = ("bf16", "fp8")
+
+
 def _load_safetensors_dir(path: str) -> dict:
     from safetensors.torch import load_file
 
@@ -27,7 +31,16 @@ def _load_safetensors_dir(path: str) -> dict:
 
 
 def build_decoder(name: str | DecoderConfig, device="cpu", dtype=torch.bfloat16, tp: TPGroup = SINGLE,
-                  seed: int = 0, checkpoint: Optional[str] = None, **overrides):
+                  seed: int = 0, checkpoint: Optional[str] = None, decode_weights: Optional[str] = None, **overrides):
+    """``decode_weights``: ``"bf16"``, or ``"fp8"`` for e4m3 copies of the decode step's weights
+    (``LlamaModel.quantize_decode_weights``: Llama on a GPU, not under TP); None reads
+    ``LK_DECODE_WEIGHTS`` (default ``bf16``)."""
+    if decode_weights is None:
+        decode_weights = os.environ.get("LK_DECODE_WEIGHTS", "") or "bf16"
+    if decode_weights not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {decode_weights!r}")
+    if decode_weights == "fp8" and tp.enabled:
+        raise ValueError("decode_weights='fp8' is not supported with tensor parallelism")
     cfg = name if isinstance(name, DecoderConfig) else decoder_config(name, **overrides)
     cls = LlamaModel if cfg.arch == "llama" else OPTModel
     m = cls(cfg, tp, dtype, device)
@@ -37,6 +50,8 @@ def build_decoder(name: str | DecoderConfig, device="cpu", dtype=torch.bfloat16,
         m.random_init(seed)
         if isinstance(m, LlamaModel) and m.device.type == "cuda" and llama.FOLD_NORMS:
             m.fold_norms()
+    if decode_weights == "fp8" and isinstance(m, LlamaModel) and m.device.type == "cuda":
+        m.quantize_decode_weights()  # after folding: the weights as the decode step reads them
     return m.eval()
 
 

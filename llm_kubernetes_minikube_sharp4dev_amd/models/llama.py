@@ -156,6 +156,7 @@ class LlamaModel(nn.Module):
             p.copy_(torch.randn(p.shape, generator=g, device=gen_dev, dtype=torch.float32).mul_(std).to(p.dtype))
         self.lm_head[self.vocab_local:].zero_()
         self.rope_neox, self.folded = True, False
+        self.drop_decode_weights()
         return self
 
     @torch.no_grad()
@@ -181,6 +182,54 @@ class LlamaModel(nn.Module):
                 g.fill_(1.0)
         self.rope_neox, self.folded = False, True
         return self
+
+    # the FP8 copies of the decode step's weights: (layer attribute, quantised, scales)
+    _W8_NAMES = (("qkv", "qkv_q", "qkv_s"), ("o", "o_q", "o_s"), ("gate_up", "gate_up_q", "gate_up_s"),
+                 ("down", "down_q", "down_s"))
+
+    @torch.no_grad()
+    def quantize_decode_weights(self):
+        """FP8 (e4m3, one fp32 scale per output row) copies of the four projections of every layer
+        and of the LM head, for decode steps of <= 2 rows (csrc/gemv_decode_w8.hip,
+        docs/decode_fp8.md).  Runs after ``fold_norms``: it quantises the weights as they are then,
+        folded and permuted.  Every other step keeps the bf16 weights, which stay in place, so this
+        costs one byte per weight of extra memory.  Not under tensor parallelism."""
+        if self.tp.enabled:
+            raise ValueError("quantize_decode_weights: FP8 decode weights are not supported under tensor parallelism")
+        for L in self.layers:
+            for name, qn, sn in self._W8_NAMES:
+                wq, ws = ops.quantize_rows_e4m3(getattr(L, name))
+                for n, t in ((qn, wq), (sn, ws)):
+                    L._buffers.pop(n, None)
+                    L.register_buffer(n, t, persistent=False)
+        wq, ws = ops.quantize_rows_e4m3(self.lm_head)  # (the padded rows: zeros with scale 1)
+        for n, t in (("lm_head_q", wq), ("lm_head_s", ws)):
+            self._buffers.pop(n, None)
+            self.register_buffer(n, t, persistent=False)
+        return self
+
+    def drop_decode_weights(self):
+        """Forget the FP8 copies (new weights were loaded: they no longer describe them)."""
+        for L in self.layers:
+            for _, qn, sn in self._W8_NAMES:
+                L._buffers.pop(qn, None)
+                L._buffers.pop(sn, None)
+        self._buffers.pop("lm_head_q", None)
+        self._buffers.pop("lm_head_s", None)
+
+    @property
+    def decode_weights(self) -> str:
+        return "fp8" if "lm_head_q" in self._buffers else "bf16"
+
+    def _w8_ok(self, M: int) -> bool:
+        """The FP8 copies exist and the FP8 GEMV takes all four projections at M rows."""
+        L0 = self.layers[0]
+        if "qkv_q" not in L0._buffers:
+            return False
+        return (ops.gemv_w8_supported(M, L0.qkv.shape[0], L0.qkv.shape[1], 3)
+                and ops.gemv_w8_supported(M, L0.o.shape[0], L0.o.shape[1], 1)
+                and ops.gemv_w8_supported(M, L0.gate_up.shape[0], L0.gate_up.shape[1], 2)
+                and ops.gemv_w8_supported(M, L0.down.shape[0], L0.down.shape[1], 1))
 
     # ------------------------------------------------------------------ forward
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
@@ -253,8 +302,18 @@ class LlamaModel(nn.Module):
         eps = cfg.norm_eps
         hq, hkv, D = self.hq, self.hkv, self.D
         attn_out = None
+        w8 = self._w8_ok(res.shape[0])
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]
+            if w8:  # the same block over the FP8 copies (csrc/gemv_decode_w8.hip)
+                qkv = ops.gemv_decode_w8(3, res, L.qkv_q, L.qkv_s, L.input_norm, eps, positions=meta.positions,
+                                         cos_sin=self.cos_sin, Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc,
+                                         slots=meta.slots, neox=self.rope_neox)
+                attn_out = paged_attention(qkv, kc, vc, meta, hq, hkv, D, self.scale, attn_out)
+                ops.gemv_decode_w8(1, attn_out, L.o_q, L.o_s, res=res)
+                a = ops.gemv_decode_w8(2, res, L.gate_up_q, L.gate_up_s, L.post_norm, eps)
+                ops.gemv_decode_w8(1, a, L.down_q, L.down_s, res=res)
+                continue
             qkv = ops.gemv_decode(3, res, L.qkv, L.input_norm, eps, positions=meta.positions, cos_sin=self.cos_sin,
                                   Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc, slots=meta.slots,
                                   neox=self.rope_neox)
@@ -415,7 +474,13 @@ class LlamaModel(nn.Module):
 
     def head(self, hidden: torch.Tensor) -> torch.Tensor:
         """This rank's vocab-shard logits [R, vocab_local] (a view of the padded GEMM output)."""
-        lg = ops.linear(hidden, self.lm_head)
+        if ("lm_head_q" in self._buffers and hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled
+                and hidden.shape[0] <= ops.GEMV_MAX_M and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0
+                and hidden.data_ptr() % 16 == 0
+                and ops.gemv_w8_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
+            lg = ops.gemv_decode_w8(0, hidden, self.lm_head_q, self.lm_head_s)
+        else:
+            lg = ops.linear(hidden, self.lm_head)
         return lg[:, : self.vocab_local] if lg.shape[1] != self.vocab_local else lg
 
     def logits(self, hidden: torch.Tensor, gather: bool = True, dtype=torch.float32) -> torch.Tensor:
@@ -442,6 +507,7 @@ class LlamaModel(nn.Module):
         TP-sliced here)."""
         cfg, tp, D = self.cfg, self.tp, self.D
         self.rope_neox, self.folded = True, False  # fresh HF-layout weights
+        self.drop_decode_weights()
 
         def t(name):
             return sd[name].to(self.dtype)

@@ -981,6 +981,93 @@ def gemv_decode(mode: int, x, w, gamma=None, eps: float = 1e-5, res=None, positi
     return qkv
 
 
+# FP8 weights for the same decode step (csrc/gemv_decode_w8.hip, docs/decode_fp8.md): W as OCP e4m3,
+# one byte per weight, one fp32 scale per output row, applied once to the finished fp32 dot product.
+E4M3_MAX = 448.0
+_GEMV_W8_OK: dict = {}
+
+
+@torch.no_grad()
+def quantize_rows_e4m3(w: torch.Tensor, block_rows: int = 8192):
+    """w [N, K] -> (wq [N, K] float8_e4m3fn, wscale f32 [N]): ``wscale[n] = max_k |w[n, k]| / 448`` (1
+    for an all-zero row), ``wq = clamp(w / wscale, -448, 448)`` rounded to nearest even.  Load-time;
+    row blocks, so no fp32 copy of a whole matrix exists.  Never produces the NaN encoding."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows_e4m3: w must be [N, K], got {tuple(w.shape)}")
+    N, K = w.shape
+    wq = torch.empty(N, K, dtype=torch.float8_e4m3fn, device=w.device)
+    wscale = torch.empty(N, dtype=torch.float32, device=w.device)
+    for r0 in range(0, N, block_rows):
+        blk = w[r0:r0 + block_rows].float()
+        s = blk.abs().amax(dim=1) / E4M3_MAX
+        s = torch.where(s > 0, s, torch.ones_like(s))
+        wscale[r0:r0 + block_rows] = s
+        wq[r0:r0 + block_rows] = (blk / s[:, None]).clamp_(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return wq, wscale
+
+
+def dequantize_rows_e4m3(wq: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] of a quantised matrix (references and tests)."""
+    q = wq.view(torch.float8_e4m3fn) if wq.dtype == torch.uint8 else wq
+    return q.float() * wscale.float()[:, None]
+
+
+def gemv_w8_supported(M: int, N: int, K: int, mode: int) -> bool:
+    key = (M, N, K, mode)
+    ok = _GEMV_W8_OK.get(key)
+    if ok is None:
+        ok = _GEMV_W8_OK[key] = bool(lib().gemv_w8_supported(M, N, K, mode))
+    return ok
+
+
+def _check_gemv_w8(mode: int, x, wq, wscale, gamma):
+    """The limits of the FP8 decode GEMV, as ValueErrors that name the argument."""
+    if mode not in (0, 1, 2, 3):
+        raise ValueError(f"gemv_decode_w8: mode must be 0..3, got {mode}")
+    if x.dim() != 2 or wq.dim() != 2 or x.shape[1] != wq.shape[1]:
+        raise ValueError(f"gemv_decode_w8: x must be [M, K] and wq [N, K], got {tuple(x.shape)} and {tuple(wq.shape)}")
+    M, K = x.shape
+    N = wq.shape[0]
+    if wq.dtype not in (torch.float8_e4m3fn, torch.uint8) or not wq.is_contiguous():
+        raise ValueError("gemv_decode_w8: wq must be contiguous float8_e4m3fn or uint8")
+    if wscale.dtype != torch.float32 or not wscale.is_contiguous() or wscale.numel() != N:
+        raise ValueError(f"gemv_decode_w8: wscale must be contiguous float32 [N = {N}]")
+    if not 1 <= M <= 2:
+        raise ValueError(f"gemv_decode_w8: M (rows of x) must be 1 or 2, got {M}")
+    if K < 1024 or K % 1024:
+        raise ValueError(f"gemv_decode_w8: K must be a multiple of 1024, got {K}")
+    if N < 2 or N % 2:
+        raise ValueError(f"gemv_decode_w8: N must be even, got {N}")
+    if x.stride(-1) != 1 or x.stride(0) % 8:
+        raise ValueError(f"gemv_decode_w8: ldx (row stride of x) must be a multiple of 8, got {x.stride(0)}")
+    for name, t in (("x", x), ("wq", wq), ("gamma", gamma)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"gemv_decode_w8: {name} must be 16-byte aligned")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError(f"gemv_decode_w8: gamma must be contiguous [K = {K}]")
+    if (M + 1) * K * 2 > 163840 - 1024:  # (room for gamma reserved, as the kernel's support check does)
+        raise ValueError(f"gemv_decode_w8: the x rows (+ gamma) at K {K} exceed the LDS limit")
+
+
+def gemv_decode_w8(mode: int, x, wq, wscale, gamma=None, eps: float = 1e-5, res=None, positions=None, cos_sin=None,
+                   Hq: int = 0, Hkv: int = 0, D: int = 0, k_cache=None, v_cache=None, slots=None, neox: bool = True):
+    """:func:`gemv_decode` over FP8 weights: ``wq`` [N, K] e4m3 (``float8_e4m3fn`` or its bytes as
+    ``uint8``), ``wscale`` f32 [N]; row n of W is ``wq[n] * wscale[n]``.  Off the GPU: the reference
+    arithmetic of :func:`gemv_decode` on the dequantised fp32 weights."""
+    _check_gemv_w8(mode, x, wq, wscale, gamma)
+    if mode == 1 and res is None:
+        raise ValueError("gemv_decode_w8: mode 1 needs res")
+    if mode == 3 and (positions is None or cos_sin is None or D <= 0 or D % 2 or wq.shape[0] != (Hq + 2 * Hkv) * D):
+        raise ValueError("gemv_decode_w8: mode 3 needs positions, cos_sin and N == (Hq + 2 Hkv) * D with even D")
+    if use_hip(x):
+        if mode == 3 and slots is None:
+            raise ValueError("gemv_decode_w8: mode 3 needs slots")
+        return lib().gemv_decode_w8(mode, x, wq, wscale, gamma, eps, res, positions, cos_sin, Hq, Hkv, D, k_cache,
+                                    v_cache, slots, neox)
+    return gemv_decode(mode, x, dequantize_rows_e4m3(wq, wscale), gamma, eps, res, positions, cos_sin, Hq, Hkv, D,
+                       k_cache, v_cache, slots, neox)
+
+
 def linear_add_rmsnorm(x, w, residual, norm_w, eps: float):
     """RMSNorm(x W^T + residual) * norm_w, with ``residual`` updated in place to
     x W^T + residual (the pre-norm block's "o / down projection -> add -> norm")."""

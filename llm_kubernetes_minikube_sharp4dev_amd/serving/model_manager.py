@@ -159,6 +159,7 @@ class ModelManager:
     def _build_generator(self, name: str, preset: str):
         ck = self.checkpoints.get(name) or self.checkpoints.get(preset)
         model = build_decoder(preset, device=self.device, seed=self.cfg.engine.seed, checkpoint=ck, dtype=self._dtype(),
+                              decode_weights=self.cfg.engine.decode_weights,
                               **({"tp": self.tp} if self.tp is not None else {}))
         return model, load_tokenizer(ck)
 
@@ -247,9 +248,12 @@ class ModelManager:
             n = c.num_layers * 12 * c.hidden * c.hidden + c.vocab_size * c.hidden
             fam = "nomic-bert" if c.arch == "nomic_bert" else "bert"
         size = f"{n / 1e9:.1f}B" if n >= 1e9 else f"{n / 1e6:.0f}M"
-        return {"format": "safetensors" if (self.checkpoints.get(name) or self.checkpoints.get(preset)) else "random-init",
-                "family": fam, "families": [fam], "parameter_size": size, "quantization_level": "BF16",
-                "params": n, "preset": preset, "kind": kind}
+        d = {"format": "safetensors" if (self.checkpoints.get(name) or self.checkpoints.get(preset)) else "random-init",
+             "family": fam, "families": [fam], "parameter_size": size, "quantization_level": "BF16",
+             "params": n, "preset": preset, "kind": kind}
+        if kind == "generate" and self.cfg.engine.decode_weights == "fp8":
+            d["decode_weights"] = "fp8_e4m3"
+        return d
 
     def shutdown(self):
         for h in {id(h): h for h in self.generators.values()}.values():
