@@ -56,6 +56,15 @@ int lk_gemv_w8_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, 
                       const int* positions, const float* cos_sin, int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc,
                       const int* slots, int BS, int neox, hipStream_t st);
 
+// gemv_decode_mxfp4.hip (the same decode GEMV over OCP MXFP4 weights: wq4 [N, K / 2] e2m1 pairs, low
+// nibble first, wexp [N, K / 32] e8m0 block scales applied by the conversion; K % 2048 == 0)
+int lk_gemv_w4_supported(int M, int N, int K, int mode);
+void lk_gemv_w4_set_plan(int pairs, int ksplit);  // measurement arms: pairs per wave (0: default), K split (-1: default)
+int lk_gemv_w4_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, float eps, const unsigned char* wq4,
+                      const unsigned char* wexp, int M, int N, int K, bf16_t* out, long ldo, bf16_t* res, long ldr,
+                      const int* positions, const float* cos_sin, int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc,
+                      const int* slots, int BS, int neox, hipStream_t st);
+
 // GEMM part only (S >= 2): f32 partial slabs part[S][M][N], for a consumer that fuses the
 // split-K reduction (lk_splitk_rmsnorm, lk_splitk_rope_kv)
 int lk_wsgemm_set_variant(int M, int N, int K, int swiglu, int variant);  // -1 = back to the default

@@ -131,8 +131,9 @@ class EngineConfig:
     capture_graphs_at_load: bool = True                # serve: capture every decode bucket up front
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128, 192, 256)
     tp_size: int = 1
-    # bf16 | fp8: e4m3 copies of the generator's weights for decode steps of 1-2 rows
-    # (docs/decode_fp8.md; one extra byte per weight, taken from the KV budget; not with TP)
+    # bf16 | fp8 | mxfp4: e4m3 / block-scaled e2m1 copies of the generator's weights for decode steps
+    # of 1-2 rows (docs/decode_fp8.md, docs/decode_mxfp4.md; one extra byte / 17/32 B per weight, taken
+    # from the KV budget; not with TP)
     decode_weights: str = "bf16"
     seed: int = 0
     # Ollama server-side sampling defaults (applied when a request sets no options)

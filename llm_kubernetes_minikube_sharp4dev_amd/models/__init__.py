@@ -16,7 +16,7 @@ from .llama import LlamaModel
 from .opt import OPTModel
 
 
-DECODE_WEIGHTS = ("bf16", "fp8")
+DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
 
 
 def _load_safetensors_dir(path: str) -> dict:
@@ -32,15 +32,15 @@ def _load_safetensors_dir(path: str) -> dict:
 
 def build_decoder(name: str | DecoderConfig, device="cpu", dtype=torch.bfloat16, tp: TPGroup = SINGLE,
                   seed: int = 0, checkpoint: Optional[str] = None, decode_weights: Optional[str] = None, **overrides):
-    """``decode_weights``: ``"bf16"``, or ``"fp8"`` for e4m3 copies of the decode step's weights
-    (``LlamaModel.quantize_decode_weights``: Llama on a GPU, not under TP); None reads
-    ``LK_DECODE_WEIGHTS`` (default ``bf16``)."""
+    """``decode_weights``: ``"bf16"``, or ``"fp8"`` (e4m3) / ``"mxfp4"`` (e2m1, block scales) for
+    quantised copies of the decode step's weights (``LlamaModel.quantize_decode_weights``: Llama on a
+    GPU, not under TP); None reads ``LK_DECODE_WEIGHTS`` (default ``bf16``)."""
     if decode_weights is None:
         decode_weights = os.environ.get("LK_DECODE_WEIGHTS", "") or "bf16"
     if decode_weights not in DECODE_WEIGHTS:
         raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {decode_weights!r}")
-    if decode_weights == "fp8" and tp.enabled:
-        raise ValueError("decode_weights='fp8' is not supported with tensor parallelism")
+    if decode_weights != "bf16" and tp.enabled:
+        raise ValueError(f"decode_weights={decode_weights!r} is not supported with tensor parallelism")
     cfg = name if isinstance(name, DecoderConfig) else decoder_config(name, **overrides)
     cls = LlamaModel if cfg.arch == "llama" else OPTModel
     m = cls(cfg, tp, dtype, device)
@@ -50,8 +50,8 @@ def build_decoder(name: str | DecoderConfig, device="cpu", dtype=torch.bfloat16,
         m.random_init(seed)
         if isinstance(m, LlamaModel) and m.device.type == "cuda" and llama.FOLD_NORMS:
             m.fold_norms()
-    if decode_weights == "fp8" and isinstance(m, LlamaModel) and m.device.type == "cuda":
-        m.quantize_decode_weights()  # after folding: the weights as the decode step reads them
+    if decode_weights != "bf16" and isinstance(m, LlamaModel) and m.device.type == "cuda":
+        m.quantize_decode_weights(decode_weights)  # after folding: the weights as the decode step reads them
     return m.eval()
 
 

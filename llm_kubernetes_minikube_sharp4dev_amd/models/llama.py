@@ -183,43 +183,54 @@ class LlamaModel(nn.Module):
         self.rope_neox, self.folded = False, True
         return self
 
-    # the FP8 copies of the decode step's weights: (layer attribute, quantised, scales)
+    # the quantised copies of the decode step's weights: (layer attribute, quantised, scales)
     _W8_NAMES = (("qkv", "qkv_q", "qkv_s"), ("o", "o_q", "o_s"), ("gate_up", "gate_up_q", "gate_up_s"),
                  ("down", "down_q", "down_s"))
+    _W4_NAMES = (("qkv", "qkv_q4", "qkv_e"), ("o", "o_q4", "o_e"), ("gate_up", "gate_up_q4", "gate_up_e"),
+                 ("down", "down_q4", "down_e"))
 
     @torch.no_grad()
-    def quantize_decode_weights(self):
-        """FP8 (e4m3, one fp32 scale per output row) copies of the four projections of every layer
-        and of the LM head, for decode steps of <= 2 rows (csrc/gemv_decode_w8.hip,
-        docs/decode_fp8.md).  Runs after ``fold_norms``: it quantises the weights as they are then,
-        folded and permuted.  Every other step keeps the bf16 weights, which stay in place, so this
-        costs one byte per weight of extra memory.  Not under tensor parallelism."""
+    def quantize_decode_weights(self, kind: str = "fp8"):
+        """Quantised copies of the four projections of every layer and of the LM head, for decode
+        steps of <= 2 rows.  ``kind="fp8"``: e4m3 with one fp32 scale per output row
+        (csrc/gemv_decode_w8.hip, docs/decode_fp8.md; one extra byte per weight).  ``kind="mxfp4"``:
+        OCP MXFP4, e2m1 with one e8m0 scale per 32 weights (csrc/gemv_decode_mxfp4.hip,
+        docs/decode_mxfp4.md; 17/32 B per weight).  One kind at a time: the other kind's copies are
+        dropped first.  Runs after ``fold_norms``: it quantises the weights as they are then, folded
+        and permuted.  Every other step keeps the bf16 weights, which stay in place.  Not under
+        tensor parallelism."""
+        if kind not in ("fp8", "mxfp4"):
+            raise ValueError(f"quantize_decode_weights: kind must be 'fp8' or 'mxfp4', got {kind!r}")
         if self.tp.enabled:
-            raise ValueError("quantize_decode_weights: FP8 decode weights are not supported under tensor parallelism")
+            raise ValueError(f"quantize_decode_weights: {kind} decode weights are not supported under tensor "
+                             "parallelism")
+        self.drop_decode_weights()
+        names, quant = (self._W8_NAMES, ops.quantize_rows_e4m3) if kind == "fp8" else (self._W4_NAMES,
+                                                                                       ops.quantize_rows_mxfp4)
         for L in self.layers:
-            for name, qn, sn in self._W8_NAMES:
-                wq, ws = ops.quantize_rows_e4m3(getattr(L, name))
-                for n, t in ((qn, wq), (sn, ws)):
-                    L._buffers.pop(n, None)
-                    L.register_buffer(n, t, persistent=False)
-        wq, ws = ops.quantize_rows_e4m3(self.lm_head)  # (the padded rows: zeros with scale 1)
-        for n, t in (("lm_head_q", wq), ("lm_head_s", ws)):
-            self._buffers.pop(n, None)
-            self.register_buffer(n, t, persistent=False)
+            for name, qn, sn in names:
+                wq, ws = quant(getattr(L, name))
+                L.register_buffer(qn, wq, persistent=False)
+                L.register_buffer(sn, ws, persistent=False)
+        # (the padded rows: zeros with scale 1 -- FP8 scale 1.0, MXFP4 E = 127)
+        wq, ws = quant(self.lm_head)
+        qn, sn = ("lm_head_q", "lm_head_s") if kind == "fp8" else ("lm_head_q4", "lm_head_e")
+        self.register_buffer(qn, wq, persistent=False)
+        self.register_buffer(sn, ws, persistent=False)
         return self
 
     def drop_decode_weights(self):
-        """Forget the FP8 copies (new weights were loaded: they no longer describe them)."""
+        """Forget the quantised copies (new weights were loaded: they no longer describe them)."""
         for L in self.layers:
-            for _, qn, sn in self._W8_NAMES:
+            for _, qn, sn in self._W8_NAMES + self._W4_NAMES:
                 L._buffers.pop(qn, None)
                 L._buffers.pop(sn, None)
-        self._buffers.pop("lm_head_q", None)
-        self._buffers.pop("lm_head_s", None)
+        for n in ("lm_head_q", "lm_head_s", "lm_head_q4", "lm_head_e"):
+            self._buffers.pop(n, None)
 
     @property
     def decode_weights(self) -> str:
-        return "fp8" if "lm_head_q" in self._buffers else "bf16"
+        return "mxfp4" if "lm_head_q4" in self._buffers else "fp8" if "lm_head_q" in self._buffers else "bf16"
 
     def _w8_ok(self, M: int) -> bool:
         """The FP8 copies exist and the FP8 GEMV takes all four projections at M rows."""
@@ -230,6 +241,16 @@ class LlamaModel(nn.Module):
                 and ops.gemv_w8_supported(M, L0.o.shape[0], L0.o.shape[1], 1)
                 and ops.gemv_w8_supported(M, L0.gate_up.shape[0], L0.gate_up.shape[1], 2)
                 and ops.gemv_w8_supported(M, L0.down.shape[0], L0.down.shape[1], 1))
+
+    def _w4_ok(self, M: int) -> bool:
+        """The MXFP4 copies exist and the MXFP4 GEMV takes all four projections at M rows."""
+        L0 = self.layers[0]
+        if "qkv_q4" not in L0._buffers:
+            return False
+        return (ops.gemv_w4_supported(M, L0.qkv.shape[0], L0.qkv.shape[1], 3)
+                and ops.gemv_w4_supported(M, L0.o.shape[0], L0.o.shape[1], 1)
+                and ops.gemv_w4_supported(M, L0.gate_up.shape[0], L0.gate_up.shape[1], 2)
+                and ops.gemv_w4_supported(M, L0.down.shape[0], L0.down.shape[1], 1))
 
     # ------------------------------------------------------------------ forward
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
@@ -303,8 +324,18 @@ class LlamaModel(nn.Module):
         hq, hkv, D = self.hq, self.hkv, self.D
         attn_out = None
         w8 = self._w8_ok(res.shape[0])
+        w4 = self._w4_ok(res.shape[0])
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]
+            if w4:  # the same block over the MXFP4 copies (csrc/gemv_decode_mxfp4.hip)
+                qkv = ops.gemv_decode_w4(3, res, L.qkv_q4, L.qkv_e, L.input_norm, eps, positions=meta.positions,
+                                         cos_sin=self.cos_sin, Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc,
+                                         slots=meta.slots, neox=self.rope_neox)
+                attn_out = paged_attention(qkv, kc, vc, meta, hq, hkv, D, self.scale, attn_out)
+                ops.gemv_decode_w4(1, attn_out, L.o_q4, L.o_e, res=res)
+                a = ops.gemv_decode_w4(2, res, L.gate_up_q4, L.gate_up_e, L.post_norm, eps)
+                ops.gemv_decode_w4(1, a, L.down_q4, L.down_e, res=res)
+                continue
             if w8:  # the same block over the FP8 copies (csrc/gemv_decode_w8.hip)
                 qkv = ops.gemv_decode_w8(3, res, L.qkv_q, L.qkv_s, L.input_norm, eps, positions=meta.positions,
                                          cos_sin=self.cos_sin, Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc,
@@ -474,11 +505,14 @@ class LlamaModel(nn.Module):
 
     def head(self, hidden: torch.Tensor) -> torch.Tensor:
         """This rank's vocab-shard logits [R, vocab_local] (a view of the padded GEMM output)."""
-        if ("lm_head_q" in self._buffers and hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled
-                and hidden.shape[0] <= ops.GEMV_MAX_M and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0
-                and hidden.data_ptr() % 16 == 0
+        gemv = (hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled and hidden.shape[0] <= ops.GEMV_MAX_M
+                and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0)
+        if (gemv and "lm_head_q" in self._buffers
                 and ops.gemv_w8_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
             lg = ops.gemv_decode_w8(0, hidden, self.lm_head_q, self.lm_head_s)
+        elif (gemv and "lm_head_q4" in self._buffers
+                and ops.gemv_w4_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
+            lg = ops.gemv_decode_w4(0, hidden, self.lm_head_q4, self.lm_head_e)
         else:
             lg = ops.linear(hidden, self.lm_head)
         return lg[:, : self.vocab_local] if lg.shape[1] != self.vocab_local else lg

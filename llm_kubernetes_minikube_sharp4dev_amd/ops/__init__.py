@@ -1068,6 +1068,117 @@ def gemv_decode_w8(mode: int, x, wq, wscale, gamma=None, eps: float = 1e-5, res=
                        k_cache, v_cache, slots, neox)
 
 
+# OCP MXFP4 weights for the same decode step (csrc/gemv_decode_mxfp4.hip, docs/decode_mxfp4.md): W as
+# e2m1, two weights per byte (weight 2j in the low nibble of byte j), one e8m0 scale byte per 32
+# consecutive weights of a row, no other scale.
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# Midpoints between neighbouring magnitudes, and whether a value exactly on one rounds up: nearest
+# even is the neighbour with mantissa bit 0 (codes 0, 2, 4, 6), so 0.25 -> 0, 0.75 -> 1, 1.25 -> 1,
+# 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.
+_E2M1_MID = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+_E2M1_TIE_UP = (False, True, False, True, False, True, False)
+MX_BLOCK = 32
+_GEMV_W4_OK: dict = {}
+
+
+@torch.no_grad()
+def quantize_rows_mxfp4(w: torch.Tensor, block_rows: int = 8192):
+    """w [N, K], K % 32 == 0 -> (wq4 uint8 [N, K / 2], wexp uint8 [N, K / 32]).  Per block of 32
+    consecutive weights of a row the OCP MX scale ``E = clamp(floor(log2(amax)) - 2 + 127, 1, 254)``
+    (127 for an all-zero block; the floor is 1, not 0, because the kernel hands the conversion an f32
+    with exponent field E and field 0 is zero, not 2^-127; 0xFF, NaN, is never written), and per
+    weight ``clamp(w / 2^(E - 127), -6, 6)`` rounded to nearest even on the e2m1 grid.  Load-time; row
+    blocks, so no fp32 copy of a whole matrix exists."""
+    if w.dim() != 2 or w.shape[1] % MX_BLOCK:
+        raise ValueError(f"quantize_rows_mxfp4: w must be [N, K] with K a multiple of 32, got {tuple(w.shape)}")
+    N, K = w.shape
+    wq4 = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    wexp = torch.empty(N, K // MX_BLOCK, dtype=torch.uint8, device=w.device)
+    for r0 in range(0, N, block_rows):
+        blk = w[r0:r0 + block_rows].float().view(-1, K // MX_BLOCK, MX_BLOCK)
+        amax = blk.abs().amax(dim=2)
+        # floor(log2(amax)) is frexp's exponent - 1 (exact for every fp32, denormals included)
+        E = (torch.frexp(amax)[1] - 1 - 2 + 127).clamp_(1, 254)
+        E = torch.where(amax > 0, E, torch.full_like(E, 127))
+        wexp[r0:r0 + block_rows] = E.to(torch.uint8)
+        # 2^(127 - E) by its exponent field (E <= 252 for finite inputs: always a normal f32); the
+        # product is exact unless it underflows, far below the first midpoint
+        inv = ((254 - E).to(torch.int32) << 23).view(torch.float32)
+        a = (blk * inv[:, :, None]).abs_().clamp_(max=6.0)
+        code = torch.zeros_like(a, dtype=torch.uint8)
+        for mid, up in zip(_E2M1_MID, _E2M1_TIE_UP):
+            code += (a >= mid) if up else (a > mid)
+        code |= (blk < 0).to(torch.uint8) << 3
+        code = code.view(-1, K // 2, 2)
+        wq4[r0:r0 + block_rows] = code[:, :, 0] | (code[:, :, 1] << 4)
+    return wq4, wexp
+
+
+def dequantize_rows_mxfp4(wq4: torch.Tensor, wexp: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] of a quantised matrix (references and tests)."""
+    N, K = wq4.shape[0], wq4.shape[1] * 2
+    code = torch.stack((wq4 & 0xF, wq4 >> 4), dim=2).view(N, K).long()
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=wq4.device)[code & 7]
+    val = torch.where((code & 8) != 0, -mag, mag).view(N, K // MX_BLOCK, MX_BLOCK)
+    scale = torch.exp2((wexp.int() - 127).double())  # (fp64: 2^-127 is no normal f32)
+    return (val.double() * scale[:, :, None]).float().view(N, K)
+
+
+def gemv_w4_supported(M: int, N: int, K: int, mode: int) -> bool:
+    key = (M, N, K, mode)
+    ok = _GEMV_W4_OK.get(key)
+    if ok is None:
+        ok = _GEMV_W4_OK[key] = bool(lib().gemv_w4_supported(M, N, K, mode))
+    return ok
+
+
+def _check_gemv_w4(mode: int, x, wq4, wexp, gamma):
+    """The limits of the MXFP4 decode GEMV, as ValueErrors that name the argument."""
+    if mode not in (0, 1, 2, 3):
+        raise ValueError(f"gemv_decode_w4: mode must be 0..3, got {mode}")
+    if x.dim() != 2 or wq4.dim() != 2 or wexp.dim() != 2:
+        raise ValueError("gemv_decode_w4: x must be [M, K], wq4 [N, K / 2] and wexp [N, K / 32]")
+    M, K = x.shape
+    N = wq4.shape[0]
+    if not 1 <= M <= 2:
+        raise ValueError(f"gemv_decode_w4: M (rows of x) must be 1 or 2, got {M}")
+    if K < 2048 or K % 2048:
+        raise ValueError(f"gemv_decode_w4: K must be a multiple of 2048, got {K}")
+    if wq4.dtype != torch.uint8 or not wq4.is_contiguous() or wq4.shape[1] != K // 2:
+        raise ValueError(f"gemv_decode_w4: wq4 must be contiguous uint8 [N, K / 2 = {K // 2}], got {tuple(wq4.shape)}")
+    if wexp.dtype != torch.uint8 or not wexp.is_contiguous() or tuple(wexp.shape) != (N, K // MX_BLOCK):
+        raise ValueError(f"gemv_decode_w4: wexp must be contiguous uint8 [N = {N}, K / 32 = {K // MX_BLOCK}]")
+    if N < 2 or N % 2:
+        raise ValueError(f"gemv_decode_w4: N must be even, got {N}")
+    if x.stride(-1) != 1 or x.stride(0) % 8:
+        raise ValueError(f"gemv_decode_w4: ldx (row stride of x) must be a multiple of 8, got {x.stride(0)}")
+    for name, t in (("x", x), ("wq4", wq4), ("gamma", gamma)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"gemv_decode_w4: {name} must be 16-byte aligned")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError(f"gemv_decode_w4: gamma must be contiguous [K = {K}]")
+    if (M + 1) * K * 2 > 163840 - 1024:  # (room for gamma reserved, as the kernel's support check does)
+        raise ValueError(f"gemv_decode_w4: the x rows (+ gamma) at K {K} exceed the LDS limit")
+
+
+def gemv_decode_w4(mode: int, x, wq4, wexp, gamma=None, eps: float = 1e-5, res=None, positions=None, cos_sin=None,
+                   Hq: int = 0, Hkv: int = 0, D: int = 0, k_cache=None, v_cache=None, slots=None, neox: bool = True):
+    """:func:`gemv_decode` over MXFP4 weights (:func:`quantize_rows_mxfp4`'s layout).  Off the GPU: the
+    reference arithmetic of :func:`gemv_decode` on the dequantised fp32 weights."""
+    _check_gemv_w4(mode, x, wq4, wexp, gamma)
+    if mode == 1 and res is None:
+        raise ValueError("gemv_decode_w4: mode 1 needs res")
+    if mode == 3 and (positions is None or cos_sin is None or D <= 0 or D % 2 or wq4.shape[0] != (Hq + 2 * Hkv) * D):
+        raise ValueError("gemv_decode_w4: mode 3 needs positions, cos_sin and N == (Hq + 2 Hkv) * D with even D")
+    if use_hip(x):
+        if mode == 3 and slots is None:
+            raise ValueError("gemv_decode_w4: mode 3 needs slots")
+        return lib().gemv_decode_w4(mode, x, wq4, wexp, gamma, eps, res, positions, cos_sin, Hq, Hkv, D, k_cache,
+                                    v_cache, slots, neox)
+    return gemv_decode(mode, x, dequantize_rows_mxfp4(wq4, wexp), gamma, eps, res, positions, cos_sin, Hq, Hkv, D,
+                       k_cache, v_cache, slots, neox)
+
+
 def linear_add_rmsnorm(x, w, residual, norm_w, eps: float):
     """RMSNorm(x W^T + residual) * norm_w, with ``residual`` updated in place to
     x W^T + residual (the pre-norm block's "o / down projection -> add -> norm")."""

@@ -251,8 +251,8 @@ class ModelManager:
         d = {"format": "safetensors" if (self.checkpoints.get(name) or self.checkpoints.get(preset)) else "random-init",
              "family": fam, "families": [fam], "parameter_size": size, "quantization_level": "BF16",
              "params": n, "preset": preset, "kind": kind}
-        if kind == "generate" and self.cfg.engine.decode_weights == "fp8":
-            d["decode_weights"] = "fp8_e4m3"
+        if kind == "generate" and self.cfg.engine.decode_weights in ("fp8", "mxfp4"):
+            d["decode_weights"] = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4_e2m1"}[self.cfg.engine.decode_weights]
         return d
 
     def shutdown(self):

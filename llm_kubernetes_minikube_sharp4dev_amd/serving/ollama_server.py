@@ -580,7 +580,7 @@ def create_app(manager: Optional[ModelManager] = None, cfg=None):
             return err(404, f"model '{name}' not found")
         caps = {"generate": ["completion"], "rerank": ["rerank"]}.get(d["kind"], ["embedding"])
         details = {k: d[k] for k in ("format", "family", "families", "parameter_size", "quantization_level")}
-        if "decode_weights" in d:  # (only with engine.decode_weights = fp8: docs/decode_fp8.md)
+        if "decode_weights" in d:  # (only with engine.decode_weights = fp8 or mxfp4)
             details["decode_weights"] = d["decode_weights"]
         return {"modelfile": f"FROM {d['preset']}\n", "parameters": "", "template": "{{ .Prompt }}",
                 "details": details,
