@@ -133,6 +133,7 @@ class LlamaModel(nn.Module):
         self._comm_stream = None  # TP prefill: the row-parallel tails' stream (_post_attn_pipelined)
         self.overlap_tails = 0    # layers whose post-attention half ran chunked + overlapped
         self.last_layer_rows = 0  # steps whose last block ran on the gathered logit rows only
+        self.gemm_w4_steps = 0    # 3 to 16 row decode steps that ran on the MXFP4 copies (MFMA kernel)
         # RoPE pairs: rotate_half (i, i + D/2) as in HF checkpoints, or adjacent (2i, 2i + 1) once
         # fold_norms has permuted the q / k rows (what the fused QKV epilogue rotates)
         self.rope_neox = True
@@ -195,7 +196,9 @@ class LlamaModel(nn.Module):
         steps of <= 2 rows.  ``kind="fp8"``: e4m3 with one fp32 scale per output row
         (csrc/gemv_decode_w8.hip, docs/decode_fp8.md; one extra byte per weight).  ``kind="mxfp4"``:
         OCP MXFP4, e2m1 with one e8m0 scale per 32 weights (csrc/gemv_decode_mxfp4.hip,
-        docs/decode_mxfp4.md; 17/32 B per weight).  One kind at a time: the other kind's copies are
+        docs/decode_mxfp4.md; 17/32 B per weight); the MXFP4 copies also serve decode steps of 3 to 16
+        rows where ``ops.gemm_w4_supported`` routes them (csrc/gemm_decode_mxfp4.hip,
+        docs/decode_mxfp4_rows.md).  One kind at a time: the other kind's copies are
         dropped first.  Runs after ``fold_norms``: it quantises the weights as they are then, folded
         and permuted.  Every other step keeps the bf16 weights, which stay in place.  Not under
         tensor parallelism."""
@@ -270,6 +273,8 @@ class LlamaModel(nn.Module):
             return self._forward_chain(res, meta, kv_caches)
         if self._gemv_ok(res, meta):
             return self._forward_decode_gemv(res, meta, kv_caches)
+        if self._gemm_w4_ok(res, meta):
+            return self._forward_decode_gemm_w4(res, meta, kv_caches)
         x = ops.rmsnorm(res, self.layers[0].input_norm, cfg.norm_eps)
         attn_out = None
         n = len(self.layers)
@@ -352,6 +357,43 @@ class LlamaModel(nn.Module):
             ops.gemv_decode(1, attn_out, L.o, res=res)
             a = ops.gemv_decode(2, res, L.gate_up, L.post_norm, eps)
             ops.gemv_decode(1, a, L.down, res=res)
+        x = ops.rmsnorm(res, self.final_norm, eps)
+        if meta.logits_idx is not None:
+            x = ops.gather_rows(x, meta.logits_idx)
+        return x
+
+    def _gemm_w4_ok(self, res: torch.Tensor, meta: AttnMeta) -> bool:
+        """Decode steps of 3 to 16 rows on one GPU run the same block on the MXFP4 copies, on the
+        MFMA kernel (``_forward_decode_gemm_w4``): ``_gemv_ok``'s conditions, the copies exist and
+        ``ops.gemm_w4_supported`` holds (and routes) all four projections."""
+        M = res.shape[0]
+        L0 = self.layers[0]
+        if not (ops.GEMV and res.is_cuda and not self.tp.enabled and self.cp_group is None
+                and ops.GEMM_W4_MIN_M <= M <= ops.GEMM_W4_MAX_M and meta.num_prefill_tokens == 0
+                and meta.num_decode == M and meta.shared_len is None and "qkv_q4" in L0._buffers):
+            return False
+        return (ops.gemm_w4_supported(M, L0.qkv.shape[0], L0.qkv.shape[1], 3, True)
+                and ops.gemm_w4_supported(M, L0.o.shape[0], L0.o.shape[1], 1)
+                and ops.gemm_w4_supported(M, L0.gate_up.shape[0], L0.gate_up.shape[1], 2, True)
+                and ops.gemm_w4_supported(M, L0.down.shape[0], L0.down.shape[1], 1)
+                and self.D % 32 == 0)
+
+    def _forward_decode_gemm_w4(self, res: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
+        """``_forward_decode_gemv``'s MXFP4 block for 3 to 16 rows (csrc/gemm_decode_mxfp4.hip): the
+        same five launches per layer and the same rounding points."""
+        self.gemm_w4_steps += 1
+        eps = self.cfg.norm_eps
+        hq, hkv, D = self.hq, self.hkv, self.D
+        attn_out = None
+        for li, L in enumerate(self.layers):
+            kc, vc = kv_caches[li]
+            qkv = ops.gemm_decode_w4(3, res, L.qkv_q4, L.qkv_e, L.input_norm, eps, positions=meta.positions,
+                                     cos_sin=self.cos_sin, Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc,
+                                     slots=meta.slots, neox=self.rope_neox)
+            attn_out = paged_attention(qkv, kc, vc, meta, hq, hkv, D, self.scale, attn_out)
+            ops.gemm_decode_w4(1, attn_out, L.o_q4, L.o_e, res=res)
+            a = ops.gemm_decode_w4(2, res, L.gate_up_q4, L.gate_up_e, L.post_norm, eps)
+            ops.gemm_decode_w4(1, a, L.down_q4, L.down_e, res=res)
         x = ops.rmsnorm(res, self.final_norm, eps)
         if meta.logits_idx is not None:
             x = ops.gather_rows(x, meta.logits_idx)
@@ -507,12 +549,19 @@ class LlamaModel(nn.Module):
         """This rank's vocab-shard logits [R, vocab_local] (a view of the padded GEMM output)."""
         gemv = (hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled and hidden.shape[0] <= ops.GEMV_MAX_M
                 and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0)
+        # 3 to 16 rows: the MXFP4 copy on the MFMA kernel (csrc/gemm_decode_mxfp4.hip)
+        rows = (ops.GEMV and hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled
+                and ops.GEMM_W4_MIN_M <= hidden.shape[0] <= ops.GEMM_W4_MAX_M
+                and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0)
         if (gemv and "lm_head_q" in self._buffers
                 and ops.gemv_w8_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
             lg = ops.gemv_decode_w8(0, hidden, self.lm_head_q, self.lm_head_s)
         elif (gemv and "lm_head_q4" in self._buffers
                 and ops.gemv_w4_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
             lg = ops.gemv_decode_w4(0, hidden, self.lm_head_q4, self.lm_head_e)
+        elif (rows and "lm_head_q4" in self._buffers
+                and ops.gemm_w4_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
+            lg = ops.gemm_decode_w4(0, hidden, self.lm_head_q4, self.lm_head_e)
         else:
             lg = ops.linear(hidden, self.lm_head)
         return lg[:, : self.vocab_local] if lg.shape[1] != self.vocab_local else lg
