@@ -538,6 +538,77 @@ at::Tensor gemm_decode_w4(int64_t mode, const at::Tensor& x, const at::Tensor& w
   return out;
 }
 
+// The FP8 projection for 3 .. 16 rows on the matrix unit (csrc/gemm_decode_w8.hip): gemv_decode_w8's
+// modes, arguments and operands; K % 256 == 0, N % 32 == 0, mode 3 with D % 32 == 0.
+at::Tensor gemm_decode_w8(int64_t mode, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wscale,
+                          const c10::optional<at::Tensor>& gamma, double eps, const c10::optional<at::Tensor>& res,
+                          const c10::optional<at::Tensor>& positions, const c10::optional<at::Tensor>& cos_sin,
+                          int64_t Hq, int64_t Hkv, int64_t D, const c10::optional<at::Tensor>& k_cache,
+                          const c10::optional<at::Tensor>& v_cache, const c10::optional<at::Tensor>& slots, bool neox) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_LASTDIM(x); CHECK_CUDA(wq); CHECK_CONTIG(wq); CHECK_CUDA(wscale);
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn || wq.scalar_type() == at::kByte,
+              "gemm_decode_w8: wq must be float8_e4m3fn or uint8");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && x.size(1) == wq.size(1), "gemm_decode_w8: x [M,K], wq [N,K]");
+  const int M = x.size(0), K = x.size(1), N = wq.size(0);
+  CHECK_F32(wscale);
+  TORCH_CHECK(wscale.is_contiguous() && wscale.numel() == N, "gemm_decode_w8: wscale must be contiguous f32 [N]");
+  TORCH_CHECK(M >= 3 && M <= 16, "gemm_decode_w8: M must be 3 .. 16, got ", M);
+  TORCH_CHECK(K >= 256 && K % 256 == 0, "gemm_decode_w8: K must be a multiple of 256, got ", K);
+  TORCH_CHECK(N >= 32 && N % 32 == 0, "gemm_decode_w8: N must be a multiple of 32, got ", N);
+  TORCH_CHECK(x.stride(0) % 8 == 0, "gemm_decode_w8: ldx (x row stride) must be a multiple of 8, got ", x.stride(0));
+  check_rows16(x, "x"); check_rows16(wq, "wq");
+  if (gamma) {
+    CHECK_CUDA(*gamma); CHECK_BF16(*gamma);
+    TORCH_CHECK(gamma->numel() == K && gamma->is_contiguous(), "gamma [K]");
+    check_rows16(*gamma, "gamma");
+  }
+  // (gemm_w8_supported also routes; what the kernel can run is lk_gemm_w8_decode's own check, its -1)
+  TORCH_CHECK(mode >= 0 && mode <= 3, "gemm_decode_w8: mode outside 0..3");
+  TORCH_CHECK(!gamma || (long)M * (2 * K + 16) + 2 * K <= 163840 - 1024, "gemm_decode_w8: ", M, " x rows + gamma of K ", K,
+              " exceed the LDS limit of the RMSNorm prologue");
+  at::Tensor out;
+  bf16_t* rp = nullptr;
+  long ldr = 0;
+  const int *pos = nullptr, *sl = nullptr;
+  const float* cs = nullptr;
+  bf16_t *kc = nullptr, *vc = nullptr;
+  int BS = 0;
+  if (mode == 0) {
+    out = at::empty({M, N}, x.options());
+  } else if (mode == 1) {
+    TORCH_CHECK(res.has_value(), "gemm_decode_w8 mode 1: res");
+    CHECK_CUDA(*res); CHECK_BF16(*res); CHECK_LASTDIM(*res);
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N && res->stride(0) % 4 == 0, "res [M, N]");
+    out = *res;
+    rp = bp(*res);
+    ldr = res->stride(0);
+  } else if (mode == 2) {
+    out = at::empty({M, N / 2}, x.options());
+  } else {
+    TORCH_CHECK(positions && cos_sin && slots, "gemm_decode_w8 mode 3: positions, cos_sin, slots");
+    CHECK_I32(*positions); CHECK_I32(*slots); CHECK_F32(*cos_sin); CHECK_CONTIG(*cos_sin);
+    CHECK_CUDA(*positions); CHECK_CUDA(*slots); CHECK_CUDA(*cos_sin);
+    TORCH_CHECK(positions->numel() >= M && slots->numel() >= M, "positions / slots: one per row");
+    TORCH_CHECK(cos_sin->dim() == 2 && cos_sin->size(1) == D, "cos_sin [P, D]");
+    TORCH_CHECK(D > 0 && D % 32 == 0 && N == (Hq + 2 * Hkv) * D, "qkv rows = (Hq + 2 Hkv) D, D a multiple of 32");
+    out = at::empty({M, N}, x.options());
+    pos = ip(*positions); sl = ip(*slots); cs = cos_sin->data_ptr<float>();
+    if (k_cache) {
+      TORCH_CHECK(v_cache.has_value(), "k_cache without v_cache");
+      CHECK_BF16(*k_cache); CHECK_BF16(*v_cache); CHECK_CONTIG(*k_cache); CHECK_CONTIG(*v_cache);
+      TORCH_CHECK(k_cache->dim() == 4 && k_cache->size(1) == Hkv && k_cache->size(3) == D &&
+                  v_cache->sizes() == k_cache->sizes(), "cache [blocks, Hkv, BS, D]");
+      kc = bp(*k_cache); vc = bp(*v_cache); BS = k_cache->size(2);
+    }
+  }
+  CHECK_RC(lk_gemm_w8_decode((int)mode, bp(x), x.stride(0), bpo(gamma), (float)eps,
+                             reinterpret_cast<const unsigned char*>(wq.data_ptr()), wscale.data_ptr<float>(), M, N, K,
+                             mode == 1 ? nullptr : bp(out), mode == 1 ? 0 : out.stride(0), rp, ldr, pos, cs, (int)Hq,
+                             (int)Hkv, (int)D, kc, vc, sl, BS, neox ? 1 : 0, cur_stream()),
+           "gemm_decode_w8");
+  return out;
+}
+
 // Prefill / encoder-regime linear (csrc/gemm.hip): epi(x [M, K] . w[N, K]^T (+ bias)).
 // epi 0 none, 1 SwiGLU (w = [Wg; Wu], out [M, N/2]), 2 bias, 3 bias+GELU(erf), 4 bias+ReLU.
 at::Tensor gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t epi,
@@ -1521,6 +1592,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "measurement arms of the MXFP4 decode GEMM: waves that split K (1, 2, 4), units per wave (1, 2), steps per "
      "register set (1, 2); 0: the plan's own",
         py::arg("kw") = 0, py::arg("units") = 0, py::arg("steps") = 0);
+  m.def("gemm_decode_w8", &gemm_decode_w8, "", py::arg("mode"), py::arg("x"), py::arg("wq"), py::arg("wscale"),
+        py::arg("gamma") = py::none(), py::arg("eps") = 1e-5, py::arg("res") = py::none(),
+        py::arg("positions") = py::none(), py::arg("cos_sin") = py::none(), py::arg("Hq") = 0, py::arg("Hkv") = 0,
+        py::arg("D") = 0, py::arg("k_cache") = py::none(), py::arg("v_cache") = py::none(),
+        py::arg("slots") = py::none(), py::arg("neox") = true);
+  m.def("gemm_w8_supported", [](int64_t M, int64_t N, int64_t K, int64_t mode, bool norm) {
+    return lk_gemm_w8_supported((int)M, (int)N, (int)K, (int)mode, norm ? 1 : 0) != 0;
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("mode"), py::arg("norm") = false);
+  m.def("gemm_w8_set_plan", [](int64_t waves, int64_t kw, int64_t units) {
+    lk_gemm_w8_set_plan((int)waves, (int)kw, (int)units);
+  }, "measurement arms of the FP8 decode GEMM: waves per workgroup (4, 8), waves that split K (1, 2, 4, 8), units "
+     "per wave (1, 2; 2 only without a K split); 0: the plan's own",
+        py::arg("waves") = 0, py::arg("kw") = 0, py::arg("units") = 0);
   m.def("ws_set_variant", [](int64_t M, int64_t N, int64_t K, bool swiglu, int64_t v) {
     CHECK_RC(lk_wsgemm_set_variant((int)M, (int)N, (int)K, swiglu ? 1 : 0, (int)v), "ws_set_variant");
   }, "weight-streaming GEMM kernel for this (M bucket, N, K, swiglu): 0 ring, 1 loader waves, -1 default",

@@ -75,6 +75,16 @@ int lk_gemm_w4_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, 
                       const int* positions, const float* cos_sin, int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc,
                       const int* slots, int BS, int neox, hipStream_t st);
 
+// gemm_decode_w8.hip (gemv_decode_w8.hip's contract and FP8 operands for M 3 .. 16 on the matrix unit:
+// e4m3 converted to bf16 in registers, v_mfma_f32_16x16x32_bf16, the row scale once per finished sum;
+// K % 256 == 0, N % 32 == 0; norm: the RMSNorm prologue's X image must fit in LDS)
+int lk_gemm_w8_supported(int M, int N, int K, int mode, int norm);
+void lk_gemm_w8_set_plan(int waves, int kw, int units);  // measurement arms (0: the plan's own)
+int lk_gemm_w8_decode(int mode, const bf16_t* x, long ldx, const bf16_t* gamma, float eps, const unsigned char* wq,
+                      const float* wscale, int M, int N, int K, bf16_t* out, long ldo, bf16_t* res, long ldr,
+                      const int* positions, const float* cos_sin, int Hq, int Hkv, int D, bf16_t* kc, bf16_t* vc,
+                      const int* slots, int BS, int neox, hipStream_t st);
+
 // GEMM part only (S >= 2): f32 partial slabs part[S][M][N], for a consumer that fuses the
 // split-K reduction (lk_splitk_rmsnorm, lk_splitk_rope_kv)
 int lk_wsgemm_set_variant(int M, int N, int K, int swiglu, int variant);  // -1 = back to the default

@@ -570,7 +570,8 @@ def _decode_weights_arg(p):
     p.add_argument("--decode-weights", choices=("bf16", "fp8", "mxfp4"), default=None,
                    help="(default: engine.decode_weights of the config, bf16) fp8 / mxfp4: decode steps of 1-2 rows "
                         "stream e4m3 / block-scaled e2m1 copies of the generator's weights (docs/decode_fp8.md, "
-                        "docs/decode_mxfp4.md); not with --tp")
+                        "docs/decode_mxfp4.md), and steps of 3-16 rows where the MFMA kernels are routed "
+                        "(docs/decode_fp8_rows.md, docs/decode_mxfp4_rows.md); not with --tp")
 
 
 def main(argv=None):

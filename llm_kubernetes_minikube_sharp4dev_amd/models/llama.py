@@ -134,6 +134,7 @@ class LlamaModel(nn.Module):
         self.overlap_tails = 0    # layers whose post-attention half ran chunked + overlapped
         self.last_layer_rows = 0  # steps whose last block ran on the gathered logit rows only
         self.gemm_w4_steps = 0    # 3 to 16 row decode steps that ran on the MXFP4 copies (MFMA kernel)
+        self.gemm_w8_steps = 0    # 3 to 16 row decode steps that ran on the FP8 copies (MFMA kernel)
         # RoPE pairs: rotate_half (i, i + D/2) as in HF checkpoints, or adjacent (2i, 2i + 1) once
         # fold_norms has permuted the q / k rows (what the fused QKV epilogue rotates)
         self.rope_neox = True
@@ -194,7 +195,9 @@ class LlamaModel(nn.Module):
     def quantize_decode_weights(self, kind: str = "fp8"):
         """Quantised copies of the four projections of every layer and of the LM head, for decode
         steps of <= 2 rows.  ``kind="fp8"``: e4m3 with one fp32 scale per output row
-        (csrc/gemv_decode_w8.hip, docs/decode_fp8.md; one extra byte per weight).  ``kind="mxfp4"``:
+        (csrc/gemv_decode_w8.hip, docs/decode_fp8.md; one extra byte per weight); the FP8 copies also
+        serve decode steps of 3 to 16 rows where ``ops.gemm_w8_supported`` routes them
+        (csrc/gemm_decode_w8.hip, docs/decode_fp8_rows.md).  ``kind="mxfp4"``:
         OCP MXFP4, e2m1 with one e8m0 scale per 32 weights (csrc/gemv_decode_mxfp4.hip,
         docs/decode_mxfp4.md; 17/32 B per weight); the MXFP4 copies also serve decode steps of 3 to 16
         rows where ``ops.gemm_w4_supported`` routes them (csrc/gemm_decode_mxfp4.hip,
@@ -275,6 +278,8 @@ class LlamaModel(nn.Module):
             return self._forward_decode_gemv(res, meta, kv_caches)
         if self._gemm_w4_ok(res, meta):
             return self._forward_decode_gemm_w4(res, meta, kv_caches)
+        if self._gemm_w8_ok(res, meta):
+            return self._forward_decode_gemm_w8(res, meta, kv_caches)
         x = ops.rmsnorm(res, self.layers[0].input_norm, cfg.norm_eps)
         attn_out = None
         n = len(self.layers)
@@ -394,6 +399,43 @@ class LlamaModel(nn.Module):
             ops.gemm_decode_w4(1, attn_out, L.o_q4, L.o_e, res=res)
             a = ops.gemm_decode_w4(2, res, L.gate_up_q4, L.gate_up_e, L.post_norm, eps)
             ops.gemm_decode_w4(1, a, L.down_q4, L.down_e, res=res)
+        x = ops.rmsnorm(res, self.final_norm, eps)
+        if meta.logits_idx is not None:
+            x = ops.gather_rows(x, meta.logits_idx)
+        return x
+
+    def _gemm_w8_ok(self, res: torch.Tensor, meta: AttnMeta) -> bool:
+        """``_gemm_w4_ok`` for the FP8 copies (``_forward_decode_gemm_w8``): ``_gemv_ok``'s conditions at
+        3 to 16 rows, the copies exist and ``ops.gemm_w8_supported`` holds (and routes) all four
+        projections."""
+        M = res.shape[0]
+        L0 = self.layers[0]
+        if not (ops.GEMV and res.is_cuda and not self.tp.enabled and self.cp_group is None
+                and ops.GEMM_W8_MIN_M <= M <= ops.GEMM_W8_MAX_M and meta.num_prefill_tokens == 0
+                and meta.num_decode == M and meta.shared_len is None and "qkv_q" in L0._buffers):
+            return False
+        return (ops.gemm_w8_supported(M, L0.qkv.shape[0], L0.qkv.shape[1], 3, True)
+                and ops.gemm_w8_supported(M, L0.o.shape[0], L0.o.shape[1], 1)
+                and ops.gemm_w8_supported(M, L0.gate_up.shape[0], L0.gate_up.shape[1], 2, True)
+                and ops.gemm_w8_supported(M, L0.down.shape[0], L0.down.shape[1], 1)
+                and self.D % 32 == 0)
+
+    def _forward_decode_gemm_w8(self, res: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
+        """``_forward_decode_gemv``'s FP8 block for 3 to 16 rows (csrc/gemm_decode_w8.hip): the same
+        five launches per layer and the same rounding points."""
+        self.gemm_w8_steps += 1
+        eps = self.cfg.norm_eps
+        hq, hkv, D = self.hq, self.hkv, self.D
+        attn_out = None
+        for li, L in enumerate(self.layers):
+            kc, vc = kv_caches[li]
+            qkv = ops.gemm_decode_w8(3, res, L.qkv_q, L.qkv_s, L.input_norm, eps, positions=meta.positions,
+                                     cos_sin=self.cos_sin, Hq=hq, Hkv=hkv, D=D, k_cache=kc, v_cache=vc,
+                                     slots=meta.slots, neox=self.rope_neox)
+            attn_out = paged_attention(qkv, kc, vc, meta, hq, hkv, D, self.scale, attn_out)
+            ops.gemm_decode_w8(1, attn_out, L.o_q, L.o_s, res=res)
+            a = ops.gemm_decode_w8(2, res, L.gate_up_q, L.gate_up_s, L.post_norm, eps)
+            ops.gemm_decode_w8(1, a, L.down_q, L.down_s, res=res)
         x = ops.rmsnorm(res, self.final_norm, eps)
         if meta.logits_idx is not None:
             x = ops.gather_rows(x, meta.logits_idx)
@@ -549,7 +591,7 @@ class LlamaModel(nn.Module):
         """This rank's vocab-shard logits [R, vocab_local] (a view of the padded GEMM output)."""
         gemv = (hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled and hidden.shape[0] <= ops.GEMV_MAX_M
                 and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0)
-        # 3 to 16 rows: the MXFP4 copy on the MFMA kernel (csrc/gemm_decode_mxfp4.hip)
+        # 3 to 16 rows: the MXFP4 / FP8 copy on its MFMA kernel (csrc/gemm_decode_mxfp4.hip, gemm_decode_w8.hip)
         rows = (ops.GEMV and hidden.is_cuda and hidden.dim() == 2 and not self.tp.enabled
                 and ops.GEMM_W4_MIN_M <= hidden.shape[0] <= ops.GEMM_W4_MAX_M
                 and hidden.stride(-1) == 1 and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0)
@@ -562,6 +604,9 @@ class LlamaModel(nn.Module):
         elif (rows and "lm_head_q4" in self._buffers
                 and ops.gemm_w4_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
             lg = ops.gemm_decode_w4(0, hidden, self.lm_head_q4, self.lm_head_e)
+        elif (rows and "lm_head_q" in self._buffers
+                and ops.gemm_w8_supported(hidden.shape[0], self.lm_head.shape[0], self.lm_head.shape[1], 0)):
+            lg = ops.gemm_decode_w8(0, hidden, self.lm_head_q, self.lm_head_s)
         else:
             lg = ops.linear(hidden, self.lm_head)
         return lg[:, : self.vocab_local] if lg.shape[1] != self.vocab_local else lg

@@ -1249,6 +1249,81 @@ def gemm_decode_w4(mode: int, x, wq4, wexp, gamma=None, eps: float = 1e-5, res=N
                        k_cache, v_cache, slots, neox)
 
 
+# The FP8 operands of gemv_decode_w8 for steps of 3 to 16 rows, on the matrix unit
+# (csrc/gemm_decode_w8.hip, docs/decode_fp8_rows.md): e4m3 converted to bf16 in registers (exact), one
+# 16-column MFMA block, the row scale once per finished fp32 sum.
+GEMM_W8_MIN_M, GEMM_W8_MAX_M = 3, 16
+_GEMM_W8_OK: dict = {}
+
+
+def gemm_w8_supported(M: int, N: int, K: int, mode: int, norm: bool = False) -> bool:
+    """The FP8 decode GEMM takes (and is routed) M rows of this projection; ``norm``: with the
+    RMSNorm prologue, whose X image must fit in LDS."""
+    key = (M, N, K, mode, bool(norm))
+    ok = _GEMM_W8_OK.get(key)
+    if ok is None:
+        ok = _GEMM_W8_OK[key] = bool(lib().gemm_w8_supported(M, N, K, mode, bool(norm)))
+    return ok
+
+
+def gemm_w8_set_plan(waves: int = 0, kw: int = 0, units: int = 0) -> None:
+    """Measurement arms of the FP8 decode GEMM (benchmarks/gemm_w8_bench.py): waves per workgroup
+    (4, 8), waves that split K (1, 2, 4, 8), units per wave (1, 2); 0: the kernel's own plan."""
+    lib().gemm_w8_set_plan(waves, kw, units)
+
+
+def _check_gemm_w8(mode: int, x, wq, wscale, gamma):
+    """The limits of the FP8 decode GEMM, as ValueErrors that name the argument."""
+    if mode not in (0, 1, 2, 3):
+        raise ValueError(f"gemm_decode_w8: mode must be 0..3, got {mode}")
+    if x.dim() != 2 or wq.dim() != 2 or x.shape[1] != wq.shape[1]:
+        raise ValueError(f"gemm_decode_w8: x must be [M, K] and wq [N, K], got {tuple(x.shape)} and {tuple(wq.shape)}")
+    M, K = x.shape
+    N = wq.shape[0]
+    if not GEMM_W8_MIN_M <= M <= GEMM_W8_MAX_M:
+        raise ValueError(f"gemm_decode_w8: M (rows of x) must be 3..16, got {M}")
+    if K < 256 or K % 256:
+        raise ValueError(f"gemm_decode_w8: K must be a multiple of 256, got {K}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"gemm_decode_w8: x must be bfloat16, got {x.dtype}")
+    if wq.dtype not in (torch.float8_e4m3fn, torch.uint8) or not wq.is_contiguous():
+        raise ValueError("gemm_decode_w8: wq must be contiguous float8_e4m3fn or uint8")
+    if wscale.dtype != torch.float32 or not wscale.is_contiguous() or wscale.numel() != N:
+        raise ValueError(f"gemm_decode_w8: wscale must be contiguous float32 [N = {N}]")
+    if N < 32 or N % 32:
+        raise ValueError(f"gemm_decode_w8: N must be a multiple of 32, got {N}")
+    if x.stride(-1) != 1 or x.stride(0) % 8:
+        raise ValueError(f"gemm_decode_w8: ldx (row stride of x) must be a multiple of 8, got {x.stride(0)}")
+    for name, t in (("x", x), ("wq", wq), ("gamma", gamma)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"gemm_decode_w8: {name} must be 16-byte aligned")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError(f"gemm_decode_w8: gamma must be contiguous [K = {K}]")
+    if gamma is not None and M * (2 * K + 16) + 2 * K > 163840 - 1024:
+        raise ValueError(f"gemm_decode_w8: {M} x rows + gamma at K {K} exceed the LDS limit of the RMSNorm prologue")
+
+
+def gemm_decode_w8(mode: int, x, wq, wscale, gamma=None, eps: float = 1e-5, res=None, positions=None, cos_sin=None,
+                   Hq: int = 0, Hkv: int = 0, D: int = 0, k_cache=None, v_cache=None, slots=None, neox: bool = True):
+    """:func:`gemv_decode_w8` for 3 to 16 rows of ``x``: the same modes, arguments and FP8 operands, on
+    the MFMA kernel (K a multiple of 256, N of 32, mode 3 with D a multiple of 32).  Off the GPU: the
+    reference arithmetic of :func:`gemv_decode` on the dequantised fp32 weights."""
+    _check_gemm_w8(mode, x, wq, wscale, gamma)
+    if mode == 1 and (res is None or tuple(res.shape) != (x.shape[0], wq.shape[0]) or res.stride(0) % 4
+                      or res.data_ptr() % 8):
+        raise ValueError("gemm_decode_w8: mode 1 needs res [M, N], 8-byte aligned with a row stride multiple of 4")
+    if mode == 3 and (positions is None or cos_sin is None or D <= 0 or D % 32 or wq.shape[0] != (Hq + 2 * Hkv) * D):
+        raise ValueError("gemm_decode_w8: mode 3 needs positions, cos_sin and N == (Hq + 2 Hkv) * D with D a "
+                         "multiple of 32")
+    if use_hip(x):
+        if mode == 3 and slots is None:
+            raise ValueError("gemm_decode_w8: mode 3 needs slots")
+        return lib().gemm_decode_w8(mode, x, wq, wscale, gamma, eps, res, positions, cos_sin, Hq, Hkv, D, k_cache,
+                                    v_cache, slots, neox)
+    return gemv_decode(mode, x, dequantize_rows_e4m3(wq, wscale), gamma, eps, res, positions, cos_sin, Hq, Hkv, D,
+                       k_cache, v_cache, slots, neox)
+
+
 def linear_add_rmsnorm(x, w, residual, norm_w, eps: float):
     """RMSNorm(x W^T + residual) * norm_w, with ``residual`` updated in place to
     x W^T + residual (the pre-norm block's "o / down projection -> add -> norm")."""
